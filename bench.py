@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: board-positions/sec for the 12-layer d=128 GoCNN training step.
 
-Contract (driver): ``python bench.py --gpus N --steps K --warmup W``.
+Contract (driver): ``python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+[--full]``.
   * N = 1: one process on cuda:0.
   * N > 1 and no WORLD_SIZE in the environment: this process is only a LAUNCHER.  Before
     anything touches the GPU (torch is not even imported) it starts
@@ -9,7 +10,7 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``.
     as a CHILD process (one rank per GPU, RCCL over xGMI), relays rank 0's single JSON line
     and exits with the child's return code (non-zero if any rank failed).  The reference's
     ``makeDataParallel`` asserts the requested GPU count the same way
-    (``/root/reference/experiments.lua:155-168``, assert at ``:157``).
+    (the reference's ``experiments.lua:155-168``, assert at ``:157``).
   * N > 1 under torch.distributed.run (WORLD_SIZE set): one rank; WORLD_SIZE must equal N and
     N must not exceed the visible device count.
 W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier + device sync on both
@@ -26,7 +27,13 @@ on one MI355X, batch=256"; global batch = 256*N).  Synthetic 19x19 positions, ra
 weights (BASELINE.json: no datasets/checkpoints available).  Top-1 accuracy on synthetic
 random labels is meaningless; the metric's accuracy half is measured separately (below).
 
-After the headline timing (never inside it) the same process measures:
+A plain run does only that: set-up, warmup, the K timed steps, ``--dump-outputs`` and the JSON
+line.  ``--dump-outputs DIR`` writes what the last timed step computed (rank 0's ``params``
+after its update, its per-board ``loss`` and its predicted moves ``pred``) as float32
+``DIR/<name>.npy``; the inputs and the initial weights are seeded, so two builds run with the
+same arguments are comparable output for output.
+
+With ``--full``, after the headline timing (never inside it) the same process also measures:
   * ``secondary``: the headline network in fp8 (12x128 fp8) and the d=256 configs (BASELINE
     configs 3-5 per GPU: 12x256 bf16 and fp8) with the same K/W and the same communicator
     (under N > 1 that is config 3/5's DP=N step);
@@ -75,6 +82,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: what the last timed step computed (rank 0: "
+                         "params after the update, per-board loss, predicted moves) as float32 "
+                         "DIR/<name>.npy.  Inputs and initial weights are seeded: the same "
+                         "arguments give the same inputs in every run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures: "
+                         "the --secondary configurations, the DP report (N > 1 or --force-dp) "
+                         "and the --accuracy-steps fixture training.  Off: the headline only")
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--channels", type=int, default=128)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
@@ -124,11 +140,12 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: hidden-layer forwards on e4m3 MX-MFMA (BASELINE config 5)")
     ap.add_argument("--secondary", default="128:fp8,256:bf16,256:fp8,256:bf16:fixture",
-                    help="after the headline: other configs as CHANNELS:DTYPE[:fixture],... "
-                         "('' = none; fixture = the reference's bundled games through the C++ "
-                         "loader, BASELINE config 4)")
+                    help="--full, after the headline: other configs as "
+                         "CHANNELS:DTYPE[:fixture],... ('' = none; fixture = the reference's "
+                         "bundled games through the C++ loader, BASELINE config 4)")
     ap.add_argument("--no-report", action="store_true",
-                    help="skip the post-timing DP report (isolated collectives, no-comm step)")
+                    help="--full: skip the post-timing DP report (isolated collectives, no-comm "
+                         "step)")
     ap.add_argument("--spinup-steps", type=int, default=300,
                     help="untimed steps BEFORE the W warmup steps (a fixed count: every rank "
                          "must run the same number of collectives): "
@@ -149,9 +166,9 @@ def parse(argv=None):
                          "reports a hang while it was on the native communicator, the "
                          "fallback run gets what is left.  Worst case: %(default)s s")
     ap.add_argument("--accuracy-steps", type=int, default=3000,
-                    help="after the timed phases (untimed): train the bench's network this many "
-                         "SGD steps (batch 64) on the reference's bundled training games and "
-                         "report top-1 / NLL on the held-out validation and test games "
+                    help="--full, after the timed phases (untimed): train the bench's network "
+                         "this many SGD steps (batch 64) on the reference's bundled training "
+                         "games and report top-1 / NLL on the held-out validation and test games "
                          "(\"accuracy\" in the JSON; rank 0 only; 0 = skip)")
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="launcher/timing/JSON path on CPU over gloo (BASELINE config 1 "
@@ -319,6 +336,16 @@ def _record(args, world, elapsed_all, flops_per_board, extra) -> dict:
     return rec
 
 
+def _dump_outputs(dirname, arrays) -> None:
+    """--dump-outputs: every array of ``arrays`` ({name: torch tensor}) as float32
+    ``dirname/<name>.npy`` (the benchmark's outputs are a few MB: nothing is sampled)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"),
+                t.detach().cpu().numpy().astype(np.float32))
+
+
 class _NoGuard:
     def phase(self, *_):
         pass
@@ -398,6 +425,9 @@ def run_cpu_dry(args) -> int:
     dp.barrier()
     elapsed_all = _gather_times(time.perf_counter() - t0, "cpu")
     guard.stop()
+    if info.rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"params": be.flat_params(),
+                                          "loss": torch.tensor([be.loss_sum() / args.batch])})
     if info.rank == 0:
         args.layers, args.channels = cfg.numLayers, cfg.channelSize
         rec = _record(args, world, elapsed_all, cfg.train_flops_per_board(),
@@ -654,6 +684,10 @@ def run_gpu(args) -> int:
     _test_hang(info.rank, "timed", comm.kind if comm is not None else "")
     elapsed_all = case.timed(args.steps, dev)
     guard.phase("report", args.phase_timeout)
+    if args.dump_outputs and info.rank == 0:
+        # what the last timed step left (copied before any later step runs)
+        _dump_outputs(args.dump_outputs, {"params": case.net.params, "loss": case.net.loss,
+                                          "pred": case.net.pred})
     phases = None
     if args.profile > 0:
         from deep_go_amd.utils import trace
@@ -682,7 +716,7 @@ def run_gpu(args) -> int:
         extra["comm"] = comm.kind
         extra["ranks_params_identical"] = consistent
         extra.update(extra_comm)
-        if not args.no_report:
+        if args.full and not args.no_report:
             extra["dp"] = _dp_report(case, comm, world, dev, args, step_ms)
     if phases:
         extra["profile_host_ms_per_step"] = phases
@@ -695,8 +729,8 @@ def run_gpu(args) -> int:
     # secondary configurations (never inside the headline's timed region): CH:DTYPE[:fixture]
     # (fixture = the reference's games through the C++ loader, BASELINE config 4), and under
     # DP the headline network on the bf16 gradient wire (labelled: the headline is fp32)
-    items = [x.split(":") for x in args.secondary.split(",") if x]
-    if (use_dp and world > 1 and args.grad_dtype == "fp32"
+    items = [x.split(":") for x in args.secondary.split(",") if x] if args.full else []
+    if (args.full and use_dp and world > 1 and args.grad_dtype == "fp32"
             and not args.no_bf16_wire_secondary):
         items.append([str(args.channels), args.dtype, "wire16"])
     sec = {}
@@ -750,7 +784,7 @@ def run_gpu(args) -> int:
         torch.cuda.empty_cache()
     if sec:
         headline["secondary"] = sec
-    if args.accuracy_steps > 0:
+    if args.full and args.accuracy_steps > 0:
         # the metric's accuracy half (train.lua:14-45,122), untimed; rank 0 trains its own
         # single-GPU copy while the other ranks wait at the barrier
         guard.phase("accuracy", args.phase_timeout)

@@ -79,7 +79,9 @@ class Experiment:
     def init(self):
         cfg = self.cfg
         torch.manual_seed(cfg.seed)
-        info = dp.init_distributed() if self.info.world > 1 else self.info
+        # (a CPU run on a machine that has GPUs reduces over gloo: it must not claim a device)
+        backend = None if self._device_kind() == "hip" else "gloo"
+        info = dp.init_distributed(backend) if self.info.world > 1 else self.info
         self.info = info
         world = info.world
         if cfg.batchSize % world:

@@ -7,10 +7,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE_DATA = "/root/reference/data"
-# the reference's bundled fixture (/root/reference/data), decoded by our own t7 reader and
-# committed as packed .npz (tools/pack_fixture.py): present wherever the repo is, including
-# the GPU box, where the reference tree is not mounted
+# the reference's bundled data directory (its t7 position files and *_game_counts.txt, 4401
+# small files) as one archive: the ref_data fixture unpacks it once per session, so the tests
+# that read the raw files need nothing outside the repository
+REFERENCE_ARCHIVE = os.path.join(ROOT, "tests", "golden", "reference_data.tar.xz")
+# the same data decoded by our own t7 reader and committed as packed .npz
+# (tools/pack_fixture.py)
 PACKED_FIXTURE = os.path.join(ROOT, "tests", "fixtures")
 
 
@@ -43,10 +45,15 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture(scope="session")
-def ref_data():
-    if not os.path.isdir(REFERENCE_DATA):
-        pytest.skip("reference fixture data not mounted")
-    return REFERENCE_DATA
+def ref_data(tmp_path_factory):
+    import tarfile
+    root = tmp_path_factory.mktemp("reference")
+    with tarfile.open(REFERENCE_ARCHIVE) as tf:
+        if hasattr(tarfile, "data_filter"):
+            tf.extractall(root, filter="data")
+        else:
+            tf.extractall(root)
+    return str(root / "data")
 
 
 @pytest.fixture(scope="session")

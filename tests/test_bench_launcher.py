@@ -53,6 +53,63 @@ def test_bench_defaults_fp32_gradient_wire_and_host_pool():
     assert ExperimentConfig().grad_dtype == "fp32"
 
 
+def test_full_is_off_by_default():
+    """A plain run is the headline only: the secondary configurations, the DP report and the
+    accuracy training (whose options keep their defaults) run under --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not bench.parse([]).full and bench.parse([]).dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_float32_and_same_from_run_to_run(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy; the inputs are
+    seeded, so two runs with the same arguments give the same arrays (the CPU oracle is
+    deterministic: bit-equal)."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = _bench("--cpu-dry-run", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch",
+                   "4", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads(r.stdout.strip())
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        names = sorted(os.listdir(tmp_path / d))
+        assert names == ["loss.npy", "params.npy"]
+        outs.append({n: np.load(tmp_path / d / n) for n in names})
+    for n, x in outs[0].items():
+        assert x.dtype == np.float32 and x.size > 0 and np.isfinite(x).all()
+        assert np.array_equal(x, outs[1][n]), n
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """One GPU, plain run: the JSON line has the headline's keys and nothing of what --full
+    adds; --dump-outputs holds the last step's parameters, losses and predicted moves."""
+    import numpy as np
+    r = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--spinup-steps", "0",
+               "--dump-outputs", str(tmp_path / "o"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert rec["unit"] == "boards/s" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 256 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+    for k in ("secondary", "accuracy", "fixture_top1", "dp"):
+        assert k not in rec
+    out = {n[:-4]: np.load(tmp_path / "o" / n) for n in os.listdir(tmp_path / "o")}
+    assert sorted(out) == ["loss", "params", "pred"]
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in out.values())
+    assert out["loss"].shape == (256,) and out["pred"].shape == (256,)
+    assert (out["loss"] > 0).all() and ((out["pred"] >= 0) & (out["pred"] < 361)).all()
+    from deep_go_amd.config import get_preset
+    from deep_go_amd.models.gocnn import ParamLayout
+    cfg = get_preset("12x128-bf16", numLayers=12, channelSize=128)
+    assert out["params"].shape == (ParamLayout(cfg).numel,)
+
+
 def test_launcher_fails_loudly_when_a_rank_fails():
     # rank 1 exits non-zero (DG_BENCH_FAIL_RANK hook): no JSON line, non-zero exit
     r = _bench("--cpu-dry-run", "--gpus", "2", "--steps", "2", "--warmup", "1",

@@ -1,7 +1,7 @@
 """C++ engine / data golden tests (SURVEY.md §4.2 items 1-3, §4.3 'Golden data tests').
 
-Uses the reference's bundled fixture (/root/reference/data, 4398 positions) read with our
-own t7 decoder; nothing from the reference is executed."""
+Uses the reference's bundled fixture (tests/golden/reference_data.tar.xz, 4398 positions)
+read with our own t7 decoder; nothing from the reference is executed."""
 import glob
 import os
 
@@ -37,11 +37,11 @@ def test_fixture_planes_bit_exact(eng, ref_data):
     assert total == 4398
 
 
-def test_t7_reencode_is_byte_identical(eng, ref_data):
+def test_t7_reencode_is_byte_identical(eng, ref_data, tmp_path):
     path = ref_data + "/test/1993/2000-03-24b.sgf/50"
     raw = open(path, "rb").read()
     d = eng.read_position(path)
-    tmp = "/tmp/dg_t7_reencode"
+    tmp = str(tmp_path / "dg_t7_reencode")
     eng.write_position(tmp, d["planes"], d["player"], d["x"], d["y"], *d["ranks"])
     assert open(tmp, "rb").read() == raw
     obj = eng.t7_loads(raw)

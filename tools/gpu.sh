@@ -6,7 +6,7 @@
 #   tests            python -m pytest tests -m gpu (verbose log: gpurun_out/tests.log)
 #   tests:EXPR       the same restricted with -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench[:ARGS]     python bench.py ARGS (default: --steps 50 --warmup 10); JSON appended to
+#   bench[:ARGS]     python bench.py --full ARGS (default: --steps 50 --warmup 10); JSON appended to
 #                    gpurun_out/bench.jsonl
 #   prof[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS (graphs off unless ARGS
 #                    says otherwise; no accuracy phase) -> gpurun_out/prof_<n>/
@@ -42,11 +42,13 @@ for step in "$@"; do
         > gpurun_out/smoke.log 2>&1
       rc=$?; tail -2 gpurun_out/smoke.log ;;
     bench)
-      timeout -k 10 300 python bench.py ${arg:---steps 50 --warmup 10} \
+      timeout -k 10 300 python bench.py --full ${arg:---steps 50 --warmup 10} \
         > gpurun_out/bench_$n.log 2>&1
       rc=$?
       grep '"metric"' gpurun_out/bench_$n.log | tee -a gpurun_out/bench.jsonl ;;
     prof)
+      # (--full: the secondary configurations are profiled too)
+      arg="--full ${arg:---steps 10 --warmup 3}"
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats \
         --output-format csv -d $R/gpurun_out/prof_$n -o run -- \
         python3 $R/bench.py --accuracy-steps 0 ${arg:---steps 10 --warmup 3} > $R/gpurun_out/prof_$n.log 2>&1)
@@ -55,6 +57,7 @@ for step in "$@"; do
       # 8 SQ counters (the per-pass limit) + 1 GRBM: MFMA busy, waits, LDS conflicts and the
       # LDS-wait / LDS-active columns (SQ_WAIT_INST_LDS, SQ_LDS_IDX_ACTIVE)
       C="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE"
+      arg="--full $arg"      # (the secondary configurations' kernels are counted too)
       (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $C \
         --output-format csv -d $R/gpurun_out/pmc_$n -o run -- \
         python3 $R/bench.py --steps 3 --warmup 1 --no-graph --accuracy-steps 0 $arg > $R/gpurun_out/pmc_$n.log 2>&1)
@@ -94,7 +97,7 @@ for step in "$@"; do
         for cfg in "${cfgs[@]}"; do
           e="${cfg%%@*}"; [ "$e" = "-" ] && e=""
           xa=""; [ "$e" != "$cfg" ] || true; case "$cfg" in *@*) xa="${cfg#*@}" ;; esac
-          out=$(env $e timeout -k 10 200 python bench.py --steps 60 --warmup 10 --accuracy-steps 0 ${AB_ARGS:-} $xa 2>/dev/null \
+          out=$(env $e timeout -k 10 200 python bench.py --full --steps 60 --warmup 10 --accuracy-steps 0 ${AB_ARGS:-} $xa 2>/dev/null \
                 | grep metric) || { rc=1; break 2; }
           echo "$cfg $(echo "$out" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], ' '.join(f'{k}={v[\"value\"]}' for k, v in d.get('secondary', {}).items()))")" \
             | tee -a gpurun_out/ab.txt

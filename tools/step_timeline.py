@@ -3,8 +3,8 @@ mode: every kernel of the second-to-last complete step (steps delimited by the
 feature expansion launch, or by the first layer's kernel where the expansion is fused into it) with its start offset, duration and queue, plus the busy time
 of the union of all kernels (so side-stream overlap is visible).
 Usage: python tools/step_timeline.py TRACE.csv [all]
-  all: one step of EACH configuration in the trace (bench.py runs the headline, then the
-  secondaries: the trace is cut where the step-delimiting kernel changes)"""
+  all: one step of EACH configuration in the trace (bench.py --full runs the headline, then
+  the secondaries: the trace is cut where the step-delimiting kernel changes)"""
 import csv
 import re
 import sys
