@@ -18,9 +18,11 @@ batch 256 needs < 1 GB of HBM, so nothing is ever re-allocated in the step.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
-from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence, Tuple
+from collections import namedtuple
+from dataclasses import dataclass, field
+from typing import Callable, Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -50,6 +52,93 @@ FP8_W_MARGIN = 1.25
 FP8_G_HEADROOM = 4.0
 FP8_GHIST = 16        # gradient amax history length (conv_fp8.hip FP8_GHIST)
 REFRESH_PARTS = 512   # weight_refresh workgroups per layer (elementwise.hip)
+
+# Columns of the int64 launch tables that are edited after the table is built.
+# Refresh row (_build_refresh_table; csrc/kernels/elementwise.hip parse_refresh_row): the
+# optional operand-copy outputs (a null pointer: that copy is not written)
+RT_WEIGHT_COPIES = {1: "wf", 2: "wd", 10: "wf8", 16: "wf_frag", 17: "wd_frag",
+                    18: "wf8_frag", 19: "wd8_frag"}
+RT_PBIAS_FRAG, RT_PBIAS = 9, 15
+# grad_update row (_gu_table; elementwise.hip dg_grad_update): the refresh row, then where
+# the layer's gradient comes from
+GU_SLAB, GU_BPART, GU_SPLITS = 20, 21, 22
+# stack rows {A, pbias, Y, mask, ...} (conv_stack2.hip, conv_stack_f8.hip): the bf16 output
+STACK_Y = 2
+
+
+@dataclass(frozen=True)
+class Knobs:
+    """The DG_* switches of the launch planner (README: knob table), read when the model is
+    built.  A switch is off for the value "0" and on for anything else, except where noted."""
+    STACK: bool = True
+    DSTACK: bool = True
+    STACK_L1: bool = True
+    L1_FRAG: bool = True
+    LAYER2: bool = True
+    LAYER2_MULTI: bool = True
+    FUSE_HEAD: bool = True
+    RELU_MASK: bool = True              # on only for the value "1"
+    L0_MASK: Optional[bool] = None      # "1" on, "0" off, anything else auto
+    L0_BIAS_SMALL: bool = True
+    DGRAD_FIRST: bool = True
+    WGRAD_GROUP: int = 16               # int(value); the model's wgrad_group argument wins
+    WGRAD_WIN: bool = True
+    SIDE_STREAM: str = "bias"           # "bias" | "none" (spelled "0" or "none")
+    FUSED_UPDATE: bool = True
+    EARLY_UPDATE: Optional[bool] = None  # unset auto, "0" off, anything else on
+    FP8_DGRAD: bool = True
+    FP8_WGRAD: bool = True
+    FP8_SR: bool = True
+
+    def __post_init__(self):
+        if self.SIDE_STREAM not in ("none", "bias"):
+            raise ValueError(f"DG_SIDE_STREAM={self.SIDE_STREAM!r}: expected 0 or bias")
+
+    @classmethod
+    def from_env(cls) -> "Knobs":
+        env = os.environ.get
+        early, side = env("DG_EARLY_UPDATE"), env("DG_SIDE_STREAM", "bias")
+        kw = {f.name: env("DG_" + f.name, "1") != "0" for f in dataclasses.fields(cls)
+              if f.type == "bool"}
+        kw.update(RELU_MASK=env("DG_RELU_MASK", "1") == "1",
+                  L0_MASK={"1": True, "0": False}.get(env("DG_L0_MASK", "")),
+                  WGRAD_GROUP=int(env("DG_WGRAD_GROUP", "16")),
+                  SIDE_STREAM={"0": "none"}.get(side, side),
+                  EARLY_UPDATE=None if early is None else early != "0")
+        return cls(**kw)
+
+
+# a conv_layer2_multi table row = the pointer arguments of one conv_layer2 launch
+L2Row = namedtuple("L2Row", "A pbias X Y mask")
+
+
+@dataclass(frozen=True)
+class Op:
+    """One native launch, ``fn(*args, stream)``, with what later planning passes need to know
+    about it; unpacks as ``(fn, args)``."""
+    fn: Callable
+    args: tuple
+    layers: Tuple[int, ...] = ()      # the conv layers it computes
+    # conv_layer2: its kind (EPI_FWD | EPI_DGRAD) and table row; conv_layer2_multi: kind, table
+    kind: Optional[int] = None
+    row: Optional[L2Row] = None
+    table: Optional[np.ndarray] = field(default=None, compare=False)
+
+    def __iter__(self):
+        return iter((self.fn, self.args))
+
+
+@dataclass
+class LayerBwd:
+    """One layer's backward launches; None / empty: that launch does not exist (it is part of
+    a grouped launch issued by the group's top layer, or of the backward-data stack)."""
+    bias: Optional[Op] = None         # bias-gradient partials (pass 1)
+    wgrad: Optional[Op] = None        # weight gradient into split-K slabs
+    reduce: Optional[Op] = None       # pass 2: slab reduce, finishes the bias gradients too
+    dgrad: List[Op] = field(default_factory=list)   # dZ of the layer below
+
+    def ops(self) -> List[Op]:
+        return [op for op in (self.bias, self.wgrad, self.reduce) if op is not None] + self.dgrad
 
 
 @dataclass
@@ -82,13 +171,15 @@ class HipGoNet:
     def __init__(self, cfg: ExperimentConfig, batch: int, device="cuda",
                  flat_params: Optional[torch.Tensor] = None, num_cus: Optional[int] = None,
                  global_batch: Optional[int] = None, wgrad_group: Optional[int] = None,
-                 grad_wire: str = "fp32", keep_act_frames: bool = False):
+                 grad_wire: str = "fp32", keep_act_frames: bool = False,
+                 knobs: Optional[Knobs] = None):
         if cfg.numLayers < 2:
             raise ValueError("HIP executor needs >= 2 layers (conv stack + head)")
         self.cfg = cfg
+        self.knobs = knobs if knobs is not None else Knobs.from_env()
         self.B = batch
         self.global_batch = global_batch or batch
-        # layers per grouped weight-gradient launch (None: DG_WGRAD_GROUP, default all);
+        # layers per grouped weight-gradient launch (None: knobs.WGRAD_GROUP, default all);
         # data parallelism splits the hidden layers into groups so the top group's
         # all-reduce runs beside the next group's launch (bench.py --wgrad-group)
         self._wgrad_group = wgrad_group
@@ -146,8 +237,9 @@ class HipGoNet:
         self._defer = False
         self._gate_issued = False   # this step's loss gate already issued (side stream)
         self._early_issued = False  # this step's early update launch issued (main stream)
-        self._early_env = os.environ.get("DG_EARLY_UPDATE")   # None: auto (fp8 window)
-        self._early_ok = self._early_env != "0"
+        # knobs.EARLY_UPDATE as the attributes that tests force it through
+        self._early_ok = self.knobs.EARLY_UPDATE is not False
+        self._early_env = {None: None, True: "1", False: "0"}[self.knobs.EARLY_UPDATE]
         self._red_src = {}    # layer -> (slab, bpart, splits, Mpad, KP, bchunks) of its pass 2
 
         # ---- per-layer plans + bf16 operand weights ----
@@ -211,7 +303,7 @@ class HipGoNet:
                 self.wf8frag[p.index] = torch.zeros(p.cout * 9 * p.cin, dtype=torch.uint8,
                                                     device=dev)
                 # the fp8 backward-data stack's operand (DG_FP8_DGRAD=0: bf16 backward-data)
-                if os.environ.get("DG_FP8_DGRAD", "1") != "0":
+                if self.knobs.FP8_DGRAD:
                     self.wd8frag[p.index] = torch.zeros_like(self.wf8frag[p.index])
 
         # ---- activation / gradient frames ----
@@ -253,10 +345,9 @@ class HipGoNet:
             # (conv_l1), which lets the dgrad stack reach layer 1 (DG_L0_MASK=0: off).  The
             # pixel-tiled first layer can too (conv_nt_ex), but its byte stores cost +13 us vs
             # the ~5 us saved (measured): there DG_L0_MASK=1 opts in
-            l0 = p.index == 0 and (os.environ.get("DG_L0_MASK", "") == "1" or (
-                os.environ.get("DG_L0_MASK", "") != "0" and self._l1_res_ok(p)))
-            if ((p.board or l0) and nxt.board_d
-                    and os.environ.get("DG_RELU_MASK", "1") == "1"):
+            l0 = p.index == 0 and (self._l1_res_ok(p) if self.knobs.L0_MASK is None
+                                   else self.knobs.L0_MASK)
+            if (p.board or l0) and nxt.board_d and self.knobs.RELU_MASK:
                 self.relu_mask[p.index] = torch.zeros((B, NUM_POINTS, p.cout // 8),
                                                       dtype=torch.uint8, device=dev)
         # MX-fp8 weight gradients of the hidden layers (conv_wgrad_win8.hip, fp8 models;
@@ -264,10 +355,10 @@ class HipGoNet:
         # input activation (e4m3) and gradient (e5m2) that the fp8 stacks write beside the
         # bf16 frames (448 rows per board); allocated by _fuse_forward_stack /
         # _fuse_dgrad_stack for the layers they cover
-        self.fp8_wgrad = self.fp8 and os.environ.get("DG_FP8_WGRAD", "1") != "0"
+        self.fp8_wgrad = self.fp8 and self.knobs.FP8_WGRAD
         # stochastic rounding of the fp8 backward-data stack's e5m2 gradients, seeded by the
         # device step counter (conv_stack_f8.hip pack_bf8x4_sr; DG_FP8_SR=0: nearest even)
-        self.fp8_sr = self.fp8 and os.environ.get("DG_FP8_SR", "1") != "0"
+        self.fp8_sr = self.fp8 and self.knobs.FP8_SR
         self.x8q: List[Optional[torch.Tensor]] = [None] * len(self.plans)
         self.dz8q: List[Optional[torch.Tensor]] = [None] * len(self.plans)
         self.fp8_scales = torch.ones(2 * len(self.plans), dtype=torch.float32, device=dev)
@@ -295,20 +386,15 @@ class HipGoNet:
         # boards/s at 12x128 when introduced, neutral at 12x256).  DG_SIDE_STREAM=0: one
         # stream.  (Two other modes — the whole wgrad chain, or partials + slab reduces,
         # on the side stream — measured slower and were removed in round 2.)
-        side_mode = os.environ.get("DG_SIDE_STREAM", "bias")
-        self.side_mode = {"0": "none"}.get(side_mode, side_mode)
-        if self.side_mode not in ("none", "bias"):
-            raise ValueError(f"DG_SIDE_STREAM={side_mode!r}: expected 0 or bias")
+        self.side_mode = self.knobs.SIDE_STREAM
         self.bchunks = self.h.bias_chunks(batch)            # per-layer bias partials
         self.bchunks_g = self.h.bias_chunks_multi(batch)    # grouped (multi-layer) ones
-        slab = torch.empty(max(p.splits * p.Mpad_w * p.KPw for p in self.plans),
-                           dtype=torch.float32, device=dev)
+        # the per-layer launches' split-K slabs and bias partials (one buffer for all layers)
+        self.slab = torch.empty(max(p.splits * p.Mpad_w * p.KPw for p in self.plans),
+                                dtype=torch.float32, device=dev)
         cmax = max(p.cout for p in self.plans)
-        bpart = torch.empty(self.bchunks * (NUM_POINTS + 19) * cmax, dtype=torch.float32,
-                            device=dev)
-        self.slabs = [slab] * len(self.plans)
-        self.bparts = [bpart] * len(self.plans)
-        self.slab = slab
+        self.bpart = torch.empty(self.bchunks * (NUM_POINTS + 19) * cmax, dtype=torch.float32,
+                                 device=dev)
 
         # ---- step I/O ----
         # one packed uint8 input buffer (planes | player | rank | labels as int32), so a step's
@@ -339,7 +425,6 @@ class HipGoNet:
         # DG_CHECK_STREAMS=1: every cross-stream hand-off bracketed by timing events, verified
         # after each eager step (utils/streamcheck.py; check_streams())
         self.sc = streamcheck.StreamCheck() if streamcheck.enabled() else None
-        self._head_red_defer = False
         self._head_red_pending = False
         self._refresh_table = self._build_refresh_table()
         self._step_refresh = None   # the per-step table (plain copies no launch reads dropped)
@@ -353,6 +438,24 @@ class HipGoNet:
         """Address of flat gradient element off in the bf16 twin (grad_wire='bf16')."""
         return self.grads16.data_ptr() + 2 * off
 
+    # Addresses of conv layer i's fp8 delayed-scaling slots (layout: the comment at self.x8):
+    # the weight scale | the scale of act[i]'s fp8 shadow (= the input scale of layer i + 1)
+    # and act[i]'s observed max | the e5m2 scale of dz[i] and its observed max
+    def _s_w(self, i: int) -> int:
+        return self.fp8_scales.data_ptr() + 4 * (2 * i)
+
+    def _s_y(self, i: int) -> int:
+        return self.fp8_scales.data_ptr() + 4 * (2 * i + 1)
+
+    def _amax(self, i: int) -> int:
+        return self.fp8_amax.data_ptr() + 4 * i
+
+    def _s_g(self, i: int) -> int:
+        return self.fp8_gscales.data_ptr() + 4 * i
+
+    def _gamax(self, i: int) -> int:
+        return self.fp8_gamax.data_ptr() + 4 * i
+
     # ------------------------------------------------------------------ planning
     def _build_refresh_table(self) -> np.ndarray:
         rows = []
@@ -360,16 +463,13 @@ class HipGoNet:
             spec = self.layout.layers[p.index]
             w = self.params[spec.w_off:spec.w_off + spec.w_numel]
             w8 = self.wf8[p.index]
-            rows.append([w.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else 0,
+            rows.append([w.data_ptr(), wf.data_ptr(), _ptr(wd),
                          p.cout, p.cin, p.k * p.k, p.cinp, p.KP, p.KPd,
-                         self.pbias_frag[p.index].data_ptr()
-                         if self.pbias_frag[p.index] is not None else 0,
-                         w8.data_ptr() if w8 is not None else 0,
-                         self.fp8_scales.data_ptr() + 8 * p.index if w8 is not None else 0,
+                         _ptr(self.pbias_frag[p.index]), _ptr(w8),
+                         self._s_w(p.index) if w8 is not None else 0,
                          self.fp8_amax_w[p.index].data_ptr() if w8 is not None else 0,
                          self.params.data_ptr() + 4 * spec.b_off,
-                         self.params.data_ptr() + 4 * spec.pos_off,
-                         self.pbias[p.index].data_ptr() if self.pbias[p.index] is not None else 0,
+                         self.params.data_ptr() + 4 * spec.pos_off, _ptr(self.pbias[p.index]),
                          _ptr(self.wfrag[p.index]), _ptr(self.wdfrag[p.index]),
                          _ptr(self.wf8frag[p.index]), _ptr(self.wd8frag[p.index])])
         return np.ascontiguousarray(np.array(rows, dtype=np.int64))
@@ -379,235 +479,198 @@ class HipGoNet:
         P = self.params.data_ptr()
         G = self.grads.data_ptr()
         f4 = 4
-        self._pre: List[Tuple[Callable, tuple]] = []
-        self._fwd: List[Tuple[Callable, tuple]] = []
-        self._fwd_owner: List[int] = []   # layer each forward launch belongs to
-        self._bwd: List[List[Tuple[Callable, tuple]]] = []  # per layer (index order)
-        self._pre.append((h.expand_features, (
+        self._pre: List[Op] = []
+        self._fwd: List[Op] = []
+        self._bwd: List[LayerBwd] = []    # per layer (index order)
+        self._pre.append(Op(h.expand_features, (
             self.planes.data_ptr(), self.player.data_ptr(), self.rank.data_ptr(),
             self.x0.data_ptr(), self.B, self.plans[0].pad, INPUT_CP)))
         # the training step's input ops (the expansion moves into the forward stack's launch
         # when that runs the first layer, below)
         self._pre_train = self._pre
         for p in self.plans:
-            spec = lay.layers[p.index]
-            xin = self.x0 if p.index == 0 else self.act[p.index - 1]
+            i = p.index
+            spec = lay.layers[i]
+            xin = (self.x0 if i == 0 else self.act[i - 1]).data_ptr()
+            y = self.act[i].data_ptr()
             x_pad = spec.pad
-            y_pad = lay.layers[p.index + 1].pad
-            nxt = self.plans[p.index + 1] if p.index + 1 < len(self.plans) else None
-            self._fwd_owner.append(p.index)
+            y_pad = lay.layers[i + 1].pad
+            bias, posb = P + spec.b_off * f4, P + spec.pos_off * f4
+            msk = _ptr(self.relu_mask[i])
+            nxt = self.plans[i + 1] if i + 1 < len(self.plans) else None
+            kind = row = None
             if p.fp8:
-                i = p.index
-                S = self.fp8_scales.data_ptr()
                 y8 = self.x8[i + 1].data_ptr() if nxt is not None and nxt.fp8 else 0
-                self._fwd.append((h.conv_board_fp8, (
+                fn, args = h.conv_board_fp8, (
                     p.k, p.bm, self.wf8[i].data_ptr(), p.KP, p.cout, p.Mpad,
-                    self.x8[i].data_ptr(), x_pad, p.cinp, self.B, self.act[i].data_ptr(), y8,
-                    y_pad, P + spec.b_off * f4, P + spec.pos_off * f4, S + (2 * i - 1) * f4,
-                    S + 2 * i * f4, S + (2 * i + 1) * f4,
-                    self.fp8_amax.data_ptr() + i * 4 if y8 else 0,
-                    self.relu_mask[i].data_ptr() if self.relu_mask[i] is not None else 0)))
-            elif p.board and p.cout == 256 and self.wfrag[p.index] is not None:
-                msk = self.relu_mask[p.index]
-                self._fwd.append((h.conv_layer2, (
-                    h.EPI_FWD, self.wfrag[p.index].data_ptr(),
-                    self.pbias_frag[p.index].data_ptr(), xin.data_ptr(),
-                    self.act[p.index].data_ptr(), msk.data_ptr() if msk is not None else 0,
-                    p.cout, self.B)))
+                    self.x8[i].data_ptr(), x_pad, p.cinp, self.B, y, y8, y_pad, bias, posb,
+                    self._s_y(i - 1), self._s_w(i), self._s_y(i), self._amax(i) if y8 else 0,
+                    msk)
+            elif p.board and p.cout == 256 and self.wfrag[i] is not None:
+                kind = h.EPI_FWD
+                row = L2Row(self.wfrag[i].data_ptr(), self.pbias_frag[i].data_ptr(), xin, y,
+                            msk)
+                fn, args = h.conv_layer2, (kind, *row, p.cout, self.B)
             elif p.board:
-                msk = self.relu_mask[p.index]
-                self._fwd.append((h.conv_board_ex, (
-                    h.EPI_FWD, p.k, p.bm, self.wf[p.index].data_ptr(), p.KP, p.cout, p.Mpad,
-                    xin.data_ptr(), x_pad, p.cinp, self.B,
-                    self.act[p.index].data_ptr(), y_pad,
-                    0, 0, self.pbias[p.index].data_ptr(), 0, 0,
-                    msk.data_ptr() if msk is not None else 0)))
+                fn, args = h.conv_board_ex, (
+                    h.EPI_FWD, p.k, p.bm, self.wf[i].data_ptr(), p.KP, p.cout, p.Mpad, xin,
+                    x_pad, p.cinp, self.B, y, y_pad, 0, 0, self.pbias[i].data_ptr(), 0, 0, msk)
             elif self._l1_res_ok(p) and self.wfrag[0] is not None:
                 # first layer on conv_l1_frag (conv_l1.hip): one board per workgroup, the
                 # input frame gathered once into a conflict-free plane layout, fragment-ordered
                 # weights streamed into VGPRs (when the forward stack does not absorb it)
                 # (the feature expansion fused into its prologue: it writes x0 itself, so the
                 # separate expansion launch leaves _pre)
-                msk = self.relu_mask[0]
-                self._fwd.append((h.conv_l1_frag, (
-                    self.wfrag[0].data_ptr(), self.pbias_frag[0].data_ptr(), xin.data_ptr(),
-                    self.B, p.cout, self.act[0].data_ptr(),
-                    msk.data_ptr() if msk is not None else 0, self.planes.data_ptr(),
-                    self.player.data_ptr(), self.rank.data_ptr())))
+                fn, args = h.conv_l1_frag, (
+                    self.wfrag[0].data_ptr(), self.pbias_frag[0].data_ptr(), xin, self.B,
+                    p.cout, y, msk, self.planes.data_ptr(), self.player.data_ptr(),
+                    self.rank.data_ptr())
             elif self._l1_res_ok(p):
                 # first layer board-resident (conv_l1.hip): the 23x23x40 input frame staged
                 # once per board instead of a 5x5x40 im2col patch per pixel and tile
-                msk = self.relu_mask[p.index]
-                self._fwd.append((h.conv_l1, (p.k, self.wf[p.index].data_ptr(), p.KP, p.cout,
-                                              p.Mpad, xin.data_ptr(), x_pad, p.cinp, self.B,
-                                              self.act[p.index].data_ptr(), y_pad,
-                                              P + spec.b_off * f4, P + spec.pos_off * f4,
-                                              msk.data_ptr() if msk is not None else 0,
-                                              self.pbias[p.index].data_ptr())))
+                fn, args = h.conv_l1, (
+                    p.k, self.wf[i].data_ptr(), p.KP, p.cout, p.Mpad, xin, x_pad, p.cinp,
+                    self.B, y, y_pad, bias, posb, msk, self.pbias[i].data_ptr())
             else:
-                msk = self.relu_mask[p.index]
-                self._fwd.append((h.conv_nt_ex, (h.EPI_FWD, p.k, p.bm, p.bn,
-                                                 self.wf[p.index].data_ptr(), p.KP, p.cout,
-                                                 p.Mpad, xin.data_ptr(), x_pad, p.cinp,
-                                                 self.npix, self.act[p.index].data_ptr(), y_pad,
-                                                 P + spec.b_off * f4, P + spec.pos_off * f4, 0,
-                                                 0, msk.data_ptr() if msk is not None else 0)))
+                fn, args = h.conv_nt_ex, (
+                    h.EPI_FWD, p.k, p.bm, p.bn, self.wf[i].data_ptr(), p.KP, p.cout, p.Mpad,
+                    xin, x_pad, p.cinp, self.npix, y, y_pad, bias, posb, 0, 0, msk)
+            self._fwd.append(Op(fn, args, (i,), kind, row))
             if nxt is not None and nxt.fp8 and not p.fp8:
                 # bf16 producer feeding an fp8 layer: quantize its output frame (owned by the
                 # consumer: a fused fp8 stack quantizes its own input)
-                i = p.index
-                self._fwd_owner.append(i + 1)
-                self._fwd.append((h.frame_to_fp8, (
-                    self.act[i].data_ptr(), self.x8[i + 1].data_ptr(), self.act[i].numel(),
-                    self.fp8_scales.data_ptr() + (2 * i + 1) * 4,
-                    self.fp8_amax.data_ptr() + i * 4)))
+                self._fwd.append(Op(h.frame_to_fp8, (
+                    y, self.x8[i + 1].data_ptr(), self.act[i].numel(), self._s_y(i),
+                    self._amax(i)), (i + 1,)))
         self._fuse_forward_stack()
         self._l2_tables = []
-        self._fwd, self._fwd_owner = self._merge_layer2_runs(self._fwd, self._fwd_owner)
-        if any(f is h.conv_l1_frag for f, _ in self._fwd):
+        self._fwd = self._merge_layer2_runs(self._fwd)
+        if any(op.fn is h.conv_l1_frag for op in self._fwd):
             # conv_l1_frag (still in the list: the forward stack did not absorb the first
             # layer) expands the features itself and writes x0: no expansion launch
-            self._pre = [op for op in self._pre if op[0] is not h.expand_features]
+            self._pre = [op for op in self._pre if op.fn is not h.expand_features]
             self._pre_train = self._pre
         hd = self.head
-        hx = self.act[-1]
-        self._head_train = (h.head, (hd.k, hx.data_ptr(), hd.pad, hd.cin, self.B,
-                                     P + hd.w_off * f4, P + hd.b_off * f4, P + hd.pos_off * f4,
-                                     self.labels.data_ptr(), self.loss.data_ptr(),
-                                     self.pred.data_ptr(), 0, self.dz[-1].data_ptr(),
-                                     self.dzp[-1], self.head_gw_part.data_ptr(),
-                                     0, self.head_dzb.data_ptr(),
-                                     int(self.cfg.head_relu), 1.0 / self.global_batch))
-        self._head_red = (h.head_reduce, (self.head_dzb.data_ptr(), self.head_gw_part.data_ptr(),
-                                          self.B, hd.k * hd.k * hd.cin, G + hd.w_off * f4,
-                                          G + hd.b_off * f4, G + hd.pos_off * f4, self._sf))
+        dz, gw, dzb = (t.data_ptr() for t in (self.dz[-1], self.head_gw_part, self.head_dzb))
+        head_in = (hd.k, self.act[-1].data_ptr(), hd.pad, hd.cin, self.B)
+        head_fin = (int(self.cfg.head_relu), 1.0 / self.global_batch)
+
+        def head_io(loss, pred):
+            return (P + hd.w_off * f4, P + hd.b_off * f4, P + hd.pos_off * f4,
+                    self.labels.data_ptr(), loss.data_ptr(), pred.data_ptr())
+        self._head_train: Optional[Op] = Op(h.head, head_in + head_io(self.loss, self.pred) + (
+            0, dz, self.dzp[-1], gw, 0, dzb) + head_fin)
+        self._head_eval = Op(h.head, head_in + head_io(self.eval_loss, self.eval_pred) + (
+            0, 0, 0, 0, 0, 0) + head_fin)
+        # the argument tail of every launch that ends with the fused head
+        head_tail = head_io(self.loss, self.pred) + (dz, gw, dzb) + head_fin
+        red = (dzb, gw, self.B, hd.k * hd.k * hd.cin, G + hd.w_off * f4, G + hd.b_off * f4,
+               G + hd.pos_off * f4)
         if self.grads16 is not None:
-            self._head_red = (h.head_reduce_w, self._head_red[1][:-1] + (
+            self._head_red = Op(h.head_reduce_w, red + (
                 self._g16(hd.w_off), self._g16(hd.b_off), self._g16(hd.pos_off), self._sf))
-        self._head_eval = (h.head, (hd.k, hx.data_ptr(), hd.pad, hd.cin, self.B,
-                                    P + hd.w_off * f4, P + hd.b_off * f4, P + hd.pos_off * f4,
-                                    self.labels.data_ptr(), self.eval_loss.data_ptr(),
-                                    self.eval_pred.data_ptr(), 0, 0, 0, 0, 0, 0,
-                                    int(self.cfg.head_relu), 1.0 / self.global_batch))
+        else:
+            self._head_red = Op(h.head_reduce, red + (self._sf,))
         # training: the head runs inside the forward stack's launch when the stack ends at the
-        # last hidden layer (its image is already in LDS; conv_stack2.hip + head_body.h);
-        # evaluation keeps the standalone head.  DG_FUSE_HEAD=0 keeps the separate launch.
+        # last hidden layer (its image is already in LDS; conv_stack2.hip + head_body.h), and
+        # _head_train is None; evaluation keeps the standalone head.  DG_FUSE_HEAD=0: separate.
         self._fwd_train = self._fwd
-        head_ok = (hd.k == 3 and hd.pad == 1 and self.dzp[-1] == 1
-                   and os.environ.get("DG_FUSE_HEAD", "1") != "0")
-        head_tail = (P + hd.w_off * f4, P + hd.b_off * f4, P + hd.pos_off * f4,
-                     self.labels.data_ptr(), self.loss.data_ptr(), self.pred.data_ptr(),
-                     self.dz[-1].data_ptr(), self.head_gw_part.data_ptr(),
-                     self.head_dzb.data_ptr(), int(self.cfg.head_relu), 1.0 / self.global_batch)
+        head_ok = hd.k == 3 and hd.pad == 1 and self.dzp[-1] == 1 and self.knobs.FUSE_HEAD
         last = len(self.plans) - 1
         if (head_ok and self.stack and self.stack[-1] == last
                 and (hd.cin == 128 or (hd.cin == 256 and self.stack_fp8))):
             first = self.stack[0]
-            fused = (h.conv_stack2_fwd_head, (
-                self._stack_table.ctypes.data, len(self._stack_table),
-                self._stack_x0.data_ptr(), int(self.stack_l1), self.B) + head_tail)
+            tab = self._stack_table
+            fused = Op(h.conv_stack2_fwd_head, (
+                tab.ctypes.data, len(tab), self._stack_x0.data_ptr(), int(self.stack_l1),
+                self.B) + head_tail)
             if self.stack_fp8:
                 # C = 128: the head on the last layer's LDS image; C = 256: on its bf16 frame,
                 # read back at the end of the same launch (conv_stack_f8.hip)
-                S, AM = self.fp8_scales.data_ptr(), self.fp8_amax.data_ptr()
-                fused = (h.conv_stack_f8_fwd_head, (
-                    hd.cin, self._stack_table.ctypes.data, len(self.stack),
-                    self.act[first - 1].data_ptr(), S + 4 * (2 * (first - 1) + 1),
-                    AM + 4 * (first - 1), self.B) + head_tail)
+                args = (hd.cin, tab.ctypes.data, len(self.stack), self.act[first - 1].data_ptr(),
+                        self._s_y(first - 1), self._amax(first - 1), self.B) + head_tail
+                fused = Op(h.conv_stack_f8_fwd_head, args)
                 if self.fp8_wgrad:
-                    fused = (h.conv_stack_f8_fwd_head_y8, fused[1] + (self._fwd_y8.ctypes.data,))
-            elif self.stack_l1 and self._stack_x0 is self.x0:
+                    fused = Op(h.conv_stack_f8_fwd_head_y8, args + (self._fwd_y8.ctypes.data,))
+            elif self.stack_l1:
                 # the feature expansion fused into the stack's first-layer prologue: the
                 # launch builds its staged input planes from the packed batch and writes the
                 # expanded frame x0 for the first layer's weight gradient (no expansion launch
                 # and no x0 gather before the stack; evaluation keeps both)
-                fused = (h.conv_stack2_fwd_head_x, (
-                    self._stack_table.ctypes.data, len(self._stack_table), self.x0.data_ptr(),
-                    self.B, self.planes.data_ptr(), self.player.data_ptr(),
-                    self.rank.data_ptr()) + head_tail)
-                self._pre_train = [op for op in self._pre if op[0] is not h.expand_features]
-            self._fwd_train = [fused if f in (h.conv_stack2_fwd, h.conv_stack_f8,
-                                              h.conv_stack_f8_y8) else (f, a)
-                               for f, a in self._fwd]
+                fused = Op(h.conv_stack2_fwd_head_x, (
+                    tab.ctypes.data, len(tab), self.x0.data_ptr(), self.B,
+                    self.planes.data_ptr(), self.player.data_ptr(), self.rank.data_ptr())
+                    + head_tail)
+                self._pre_train = [op for op in self._pre if op.fn is not h.expand_features]
+            self._fwd_train = [dataclasses.replace(fused, layers=op.layers)
+                               if op is self._stack_op else op for op in self._fwd]
+            self._head_train = None
         elif (head_ok and hd.cin == 256 and self._fwd
-              and self._fwd[-1][0] is h.conv_layer2_multi
-              and self._fwd[-1][1][0] == h.EPI_FWD
-              and any(t.ctypes.data == self._fwd[-1][1][1]
-                      and int(t[-1, 3]) == self.act[-1].data_ptr() for t in self._l2_tables)):
+              and self._fwd[-1].fn is h.conv_layer2_multi and self._fwd[-1].kind == h.EPI_FWD
+              and self._fwd[-1].layers[-1] == last):
             # d = 256 bf16: the policy head at the end of the forward run's launch
             # (conv_layer2_multi HEAD: each board's head on the frame its workgroup just wrote)
-            _, a = self._fwd[-1]
-            self._fwd_train = self._fwd[:-1] + [(h.conv_layer2_multi_head,
-                                                 (a[1], a[2], self.B) + head_tail)]
-        if any(f in (h.conv_stack2_fwd_head, h.conv_stack2_fwd_head_x,
-                     h.conv_stack_f8_fwd_head, h.conv_stack_f8_fwd_head_y8,
-                     h.conv_layer2_multi_head)
-               for f, _ in self._fwd_train):
-            self._head_train = (self._noop, ())
+            run = self._fwd[-1]
+            self._fwd_train = self._fwd[:-1] + [Op(
+                h.conv_layer2_multi_head,
+                (run.table.ctypes.data, len(run.table), self.B) + head_tail, run.layers)]
+            self._head_train = None
         for p in self.plans:
-            spec = lay.layers[p.index]
             i = p.index
-            ops = []
-            dzp = self.dzp[i]
+            spec = lay.layers[i]
+            dzi, dzp = self.dz[i].data_ptr(), self.dzp[i]
             xin = self.x0 if i == 0 else self.act[i - 1]
+            b = LayerBwd()
             # bias grads: pass 1 (per board-chunk partials); pass 2 runs inside the slab
             # reduce launch, which also finalises the weight grad
-            slab, bpart = self.slabs[i].data_ptr(), self.bparts[i].data_ptr()
+            slab, bpart = self.slab.data_ptr(), self.bpart.data_ptr()
             bch = self.bchunks
-            if i == 0 and os.environ.get("DG_L0_BIAS_SMALL", "1") != "0":
+            if i == 0 and self.knobs.L0_BIAS_SMALL:
                 # the first layer's partials on the multi-layer kernel's 256-thread,
                 # 48-VGPR workgroups (64-board chunks): they fit beside the window kernel's
                 # workgroups, where the single-layer launch's 600-thread ones wait for free
                 # CUs (12x256 bf16: 552 us on the side stream's critical chain)
-                self._l0_btab = np.ascontiguousarray(
-                    np.array([[self.dz[i].data_ptr(), bpart, 0]], dtype=np.int64))
+                self._l0_btab = np.ascontiguousarray(np.array([[dzi, bpart, 0]], dtype=np.int64))
                 bch = self.bchunks_g
-                ops.append((h.bias_grad_partial_multi, (self._l0_btab.ctypes.data, 1, self.B,
-                                                        p.cout, dzp, self._sf)))
+                b.bias = Op(h.bias_grad_partial_multi, (self._l0_btab.ctypes.data, 1, self.B,
+                                                        p.cout, dzp, self._sf), (i,))
             else:
-                ops.append((h.bias_grad_partial, (self.dz[i].data_ptr(), self.B, p.cout, dzp,
-                                                  bpart)))
+                b.bias = Op(h.bias_grad_partial, (dzi, self.B, p.cout, dzp, bpart), (i,))
             # (the first layer's 5x5 as a sliding window over its 23 x 23 input frames was
             # measured slower: profiles/r4_s1_wgrad_l0_window_ab.txt)
-            ops.append((h.conv_wgrad, (p.k, self.dz[i].data_ptr(), dzp, p.cout, p.Mpad_w,
-                                       xin.data_ptr(), spec.pad, p.cinp, self.B, p.KPw,
-                                       p.splits, slab)))
+            b.wgrad = Op(h.conv_wgrad, (p.k, dzi, dzp, p.cout, p.Mpad_w, xin.data_ptr(),
+                                        spec.pad, p.cinp, self.B, p.KPw, p.splits, slab), (i,))
             red = (slab, G + spec.w_off * f4, p.splits, p.cout, p.Mpad_w, p.KPw, p.k * p.k,
                    p.cin, p.cinp, bpart, bch, G + spec.pos_off * f4,
                    G + spec.b_off * f4)
             self._red_src[i] = (slab, bpart, p.splits, p.Mpad_w, p.KPw, bch)
             if self.grads16 is not None:
-                ops.append((h.wgrad_reduce_w, red + (self._g16(spec.w_off),
-                                                     self._g16(spec.pos_off),
-                                                     self._g16(spec.b_off), self._sf)))
+                b.reduce = Op(h.wgrad_reduce_w, red + (
+                    self._g16(spec.w_off), self._g16(spec.pos_off), self._g16(spec.b_off),
+                    self._sf), (i,))
             else:
-                ops.append((h.wgrad_reduce, red + (self._sf,)))
+                b.reduce = Op(h.wgrad_reduce, red + (self._sf,), (i,))
             if i > 0:
-                prev = lay.layers[i - 1]
+                dzo, msk = self.dz[i - 1].data_ptr(), self.relu_mask[i - 1]
                 if (p.board_d and self.wdfrag[i] is not None and p.cout == 256
-                        and self.relu_mask[i - 1] is not None and self.dzp[i] == 1
-                        and self.dzp[i - 1] == 1):
-                    ops.append((h.conv_layer2, (
-                        h.EPI_DGRAD, self.wdfrag[i].data_ptr(), 0, self.dz[i].data_ptr(),
-                        self.dz[i - 1].data_ptr(), self.relu_mask[i - 1].data_ptr(), p.cout,
-                        self.B)))
+                        and msk is not None and dzp == 1 and self.dzp[i - 1] == 1):
+                    row = L2Row(self.wdfrag[i].data_ptr(), 0, dzi, dzo, msk.data_ptr())
+                    b.dgrad = [Op(h.conv_layer2, (h.EPI_DGRAD, *row, p.cout, self.B), (i,),
+                                  h.EPI_DGRAD, row)]
                 elif p.board_d:
-                    msk = self.relu_mask[i - 1]
-                    ops.append((h.conv_board_ex, (
+                    b.dgrad = [Op(h.conv_board_ex, (
                         h.EPI_DGRAD, p.k, p.bm_d, self.wd[i].data_ptr(), p.KPd, p.cin, p.Mpad_d,
-                        self.dz[i].data_ptr(), dzp, p.cout, self.B, self.dz[i - 1].data_ptr(),
-                        self.dzp[i - 1], 0, 0, 0,
+                        dzi, dzp, p.cout, self.B, dzo, self.dzp[i - 1], 0, 0, 0,
                         0 if msk is not None else self.act[i - 1].data_ptr(), spec.pad,
-                        msk.data_ptr() if msk is not None else 0)))
+                        _ptr(msk)), (i,))]
                 else:
-                    ops.append((h.conv_nt, (h.EPI_DGRAD, p.k, p.bm_d, p.bn_d,
-                                            self.wd[i].data_ptr(), p.KPd, p.cin, p.Mpad_d,
-                                            self.dz[i].data_ptr(), dzp, p.cout, self.npix,
-                                            self.dz[i - 1].data_ptr(), self.dzp[i - 1], 0, 0,
-                                            self.act[i - 1].data_ptr(), spec.pad)))
-            self._bwd.append(ops)
+                    b.dgrad = [Op(h.conv_nt, (
+                        h.EPI_DGRAD, p.k, p.bm_d, p.bn_d, self.wd[i].data_ptr(), p.KPd, p.cin,
+                        p.Mpad_d, dzi, dzp, p.cout, self.npix, dzo, self.dzp[i - 1], 0, 0,
+                        self.act[i - 1].data_ptr(), spec.pad), (i,))]
+            self._bwd.append(b)
         self._fuse_dgrad_stack()
-        self._bwd_pre, _ = self._merge_layer2_runs(self._bwd_pre)
+        self._bwd_pre = self._merge_layer2_runs(self._bwd_pre)
         self._drop_unread_act_frames()
 
     def _drop_unread_act_frames(self):
@@ -616,66 +679,58 @@ class HipGoNet:
         the e4m3 copies, the backward-data chain the ReLU bits), null those rows' Y so the
         stack skips their dequantized bf16 copy-out (conv_stack_f8.hip MODE 16).
         ``self.act_frames_dropped`` lists the layers whose act frame is then not written."""
-        self.act_frames_dropped = []
-        self.dz_frames_dropped = []
-        t = getattr(self, "_stack_table", None)
-        if (not self.keep_act_frames and self.stack_fp8 and getattr(self, "_fwd_y8", None)
-                is not None and isinstance(t, np.ndarray) and len(t) > 1):
+        def drop(t, y8) -> bool:
+            """Null the bf16 outputs of stack table t's non-last rows unless another launch
+            reads one of them."""
+            if self.keep_act_frames or y8 is None or t is None or len(t) <= 1:
+                return False
             used = self._op_pointers(exclude=(t,))   # pointers read by every OTHER launch
-            ys = [int(v) for v in t[:-1, 2]]
-            if not any(y in used for y in ys):
-                t[:-1, 2] = 0
-                self.act_frames_dropped = list(self.stack[:-1])
+            if any(int(y) in used for y in t[:-1, STACK_Y]):
+                return False
+            t[:-1, STACK_Y] = 0
+            return True
+        fwd = self.stack_fp8 and drop(getattr(self, "_stack_table", None),
+                                      getattr(self, "_fwd_y8", None))
+        self.act_frames_dropped = list(self.stack[:-1]) if fwd else []
         # the same for the fp8 backward-data stack's bf16 dZ frames (rows i -> dz[i - 1]):
         # the MX-fp8 weight gradients and the bias partials read the e5m2 copies instead
-        t = getattr(self, "_dstack_table", None)
-        if (not self.keep_act_frames and self.dstack_fp8 and getattr(self, "_dstack_y8", None)
-                is not None and isinstance(t, np.ndarray) and len(t) > 1):
-            used = self._op_pointers(exclude=(t,))
-            ys = [int(v) for v in t[:-1, 2]]
-            if not any(y in used for y in ys):
-                t[:-1, 2] = 0
-                self.dz_frames_dropped = [i - 1 for i in self.dstack[:-1]]
+        bwd = self.dstack_fp8 and drop(getattr(self, "_dstack_table", None),
+                                       getattr(self, "_dstack_y8", None))
+        self.dz_frames_dropped = [i - 1 for i in self.dstack[:-1]] if bwd else []
 
-    def _merge_layer2_runs(self, ops, owners=None):
+    def _merge_layer2_runs(self, ops: List[Op]) -> List[Op]:
         """Consecutive conv_layer2 launches of one kind whose layers chain (X of the next =
         Y of the previous) become ONE conv_layer2_multi launch: one workgroup per board runs
         the whole run, the second output half of a layer starts on a prefetched input chunk
         and the epilogue stores drain under the next half's MFMAs (csrc/kernels/
         conv_layer2.hip; bit-identical outputs).  DG_LAYER2_MULTI=0: per-layer launches."""
         h = self.h
-        owners = list(owners) if owners is not None else [None] * len(ops)
-        if os.environ.get("DG_LAYER2_MULTI", "1") == "0":
-            return ops, owners
-        out, out_own, run = [], [], []
+        if not self.knobs.LAYER2_MULTI:
+            return ops
+        out, run = [], []
 
         def flush():
             if len(run) >= 2:
-                a0 = run[0][0][1]
-                rows = [[a[1], a[2], a[3], a[4], a[5]] for (_, a), _ in run]
-                tab = np.ascontiguousarray(np.array(rows, dtype=np.int64))
+                tab = np.ascontiguousarray(np.array([op.row for op in run], dtype=np.int64))
                 self._l2_tables.append(tab)
-                out.append((h.conv_layer2_multi, (a0[0], tab.ctypes.data, len(run), a0[6],
-                                                  a0[7])))
-                out_own.append(run[0][1])
+                layers = tuple(i for op in run for i in op.layers)
+                out.append(Op(h.conv_layer2_multi, (
+                    run[0].kind, tab.ctypes.data, len(run), self.plans[layers[0]].cout, self.B),
+                    layers, run[0].kind, table=tab))
             else:
-                for op, ow in run:
-                    out.append(op)
-                    out_own.append(ow)
+                out.extend(run)
             run.clear()
-        for op, ow in zip(ops, owners):
-            f, a = op
-            if f is h.conv_layer2:
-                if run and (a[0] != run[-1][0][1][0] or a[3] != run[-1][0][1][4]
+        for op in ops:
+            if op.fn is h.conv_layer2:
+                if run and (op.kind != run[-1].kind or op.row.X != run[-1].row.Y
                             or len(run) == 16):
                     flush()
-                run.append((op, ow))
+                run.append(op)
             else:
                 flush()
                 out.append(op)
-                out_own.append(ow)
         flush()
-        return out, out_own
+        return out
 
     def _fuse_forward_stack(self):
         """Replace the per-layer forward launches of the longest run of hidden 128->128 3x3
@@ -684,7 +739,8 @@ class HipGoNet:
         self.stack = []
         self.stack_fp8 = False
         self.stack_l1 = False
-        if os.environ.get("DG_STACK", "1") == "0":
+        self._stack_op: Optional[Op] = None
+        if not self.knobs.STACK:
             return
         L = self.layout.layers
         fp8 = self.fp8
@@ -714,14 +770,14 @@ class HipGoNet:
                 m = self.relu_mask[i] = torch.zeros((self.B, NUM_POINTS, self.plans[i].cout // 8),
                                                     dtype=torch.uint8, device=self.device)
             if fp8:
-                S, AM = self.fp8_scales.data_ptr(), self.fp8_amax.data_ptr()
                 rows.append([self.wf8frag[i].data_ptr(), self.pbias_frag[i].data_ptr(),
                              self.act[i].data_ptr(), m.data_ptr(),
-                             S + 4 * (2 * i - 1), S + 4 * 2 * i, S + 4 * (2 * i + 1), AM + 4 * i])
+                             self._s_y(i - 1), self._s_w(i), self._s_y(i), self._amax(i)])
             else:
                 rows.append([self.wfrag[i].data_ptr(), self.pbias_frag[i].data_ptr(),
-                             self.act[i].data_ptr(), m.data_ptr() if m is not None else 0])
+                             self.act[i].data_ptr(), _ptr(m)])
         first = best[0]
+        members = tuple(best)
         # the first layer in front of the stack (conv_stack2.hip l1 mode): its input frame is
         # the expanded network input, its output act[0] leaves by the stack's copy-out
         self.stack_l1 = (not fp8 and first == 1 and self.wfrag[0] is not None
@@ -729,22 +785,18 @@ class HipGoNet:
         if self.stack_l1:
             rows.insert(0, [self.wfrag[0].data_ptr(), self.pbias_frag[0].data_ptr(),
                             self.act[0].data_ptr(), self.relu_mask[0].data_ptr()])
+            members = (0,) + members
         self._stack_table = np.ascontiguousarray(np.array(rows, dtype=np.int64))
         self._stack_x0 = self.x0 if self.stack_l1 else self.act[first - 1]
-        if self.stack_l1:
-            members_l1 = {0}
-        else:
-            members_l1 = set()
         if fp8:
             # fp8 forward stack (conv_stack_f8.hip): quantizes its bf16 input frame itself
             # (amax -> fp8_amax[first - 1]), dequantized bf16 activations + ReLU bits out;
             # with the fp8 weight gradients also the raw e4m3 input of every stack layer
             # (x8q[l], l in the stack: the quantized input, then each non-last output)
-            S, AM = self.fp8_scales.data_ptr(), self.fp8_amax.data_ptr()
+            fn = self.h.conv_stack_f8
             args = (self.plans[first].cout, self.h.EPI_FWD, self._stack_table.ctypes.data,
-                    len(best), self.act[first - 1].data_ptr(), S + 4 * (2 * (first - 1) + 1),
-                    AM + 4 * (first - 1), self.B)
-            op = (self.h.conv_stack_f8, args)
+                    len(best), self.act[first - 1].data_ptr(), self._s_y(first - 1),
+                    self._amax(first - 1), self.B)
             if self.fp8_wgrad:
                 for i in best:
                     self.x8q[i] = torch.zeros(self.B * FP8_PITCH * self.plans[i].cin,
@@ -752,23 +804,16 @@ class HipGoNet:
                 y8 = [self.x8q[first].data_ptr()] + [
                     self.x8q[i + 1].data_ptr() if i != best[-1] else 0 for i in best]
                 self._fwd_y8 = np.ascontiguousarray(np.array(y8, dtype=np.int64))
-                op = (self.h.conv_stack_f8_y8, args + (self._fwd_y8.ctypes.data,))
+                fn, args = self.h.conv_stack_f8_y8, args + (self._fwd_y8.ctypes.data,)
             self.stack_fp8 = True
         else:
-            op = (self.h.conv_stack2_fwd, (self._stack_table.ctypes.data, len(rows),
-                                          self._stack_x0.data_ptr(), int(self.stack_l1),
-                                          self.B))
-        # every launch owned by a stack layer goes; the stack launch takes the first's place
-        members = set(best) | members_l1
-        keep, placed = [], False
-        for fop, owner in zip(self._fwd, self._fwd_owner):
-            if owner in members:
-                if not placed:
-                    keep.append(op)
-                    placed = True
-            else:
-                keep.append(fop)
-        self._fwd = keep
+            fn = self.h.conv_stack2_fwd
+            args = (self._stack_table.ctypes.data, len(rows), self._stack_x0.data_ptr(),
+                    int(self.stack_l1), self.B)
+        self._stack_op = Op(fn, args, members)
+        # the launches of the stack's layers (consecutive in _fwd) become the stack launch
+        mine = [k for k, op in enumerate(self._fwd) if set(op.layers) <= set(members)]
+        self._fwd[mine[0]:mine[-1] + 1] = [self._stack_op]
 
     def _fuse_dgrad_stack(self):
         """Run the backward-data chain of the longest run of hidden 128->128 3x3 layers as
@@ -778,14 +823,13 @@ class HipGoNet:
         gradients run afterwards (they only read dZ_i).  DG_DSTACK=0 keeps per-layer dgrads."""
         self.dstack: List[int] = []
         self.dstack_fp8 = False
-        self.wgroups: List[List[int]] = []
-        self._bwd_pre: List[Tuple[Callable, tuple]] = []
+        self.wgroups: List[List[int]] = []       # grouped weight-gradient launches
+        self.win_groups, self.win8_groups = set(), set()   # (_group_wgrads)
+        self._bwd_pre: List[Op] = []
         self._dgrad_first = False  # every dZ (down to dZ_0) produced in _bwd_pre
         self._dz8_exact = set()    # layers whose e5m2 gradient copy equals their bf16 dZ
         self._l0_side_at = None    # group top whose backward also runs layer 0's chain
-        self._pre_dgrads = {}      # layer -> its dgrad ops moved into _bwd_pre
-        self._l0_dgrad = []        # layer 1's dgrad (-> dZ_0) when it runs on the side stream
-        if os.environ.get("DG_DSTACK", "1") == "0":
+        if not self.knobs.DSTACK:
             self._dgrads_first()
             return
         L = self.layout.layers
@@ -813,55 +857,56 @@ class HipGoNet:
             return
         self.dstack = run
         self.dstack_fp8 = fp8
+        top = run[0]
         if fp8:
-            S = self.fp8_scales.data_ptr()
-            GS, GA = self.fp8_gscales.data_ptr(), self.fp8_gamax.data_ptr()
             rows = [[self.wd8frag[i].data_ptr(), 0, self.dz[i - 1].data_ptr(),
-                     self.relu_mask[i - 1].data_ptr(), GS + 4 * i, S + 4 * 2 * i,
-                     GS + 4 * (i - 1), GA + 4 * (i - 1)] for i in run]
+                     self.relu_mask[i - 1].data_ptr(), self._s_g(i), self._s_w(i),
+                     self._s_g(i - 1), self._gamax(i - 1)] for i in run]
             self._dstack_table = np.ascontiguousarray(np.array(rows, dtype=np.int64))
-            args = (self.plans[run[0]].cout, self._dstack_table.ctypes.data,
-                    len(run), self.dz[run[0]].data_ptr(), GS + 4 * run[0], GA + 4 * run[0],
-                    self.B)
-            sr = self.step_count.data_ptr() if self.fp8_sr else 0
+            y8 = 0
             if self.fp8_wgrad:
                 # the raw e5m2 gradient of every run layer for the fp8 weight gradients:
                 # dz8q[top] = the quantized input, dz8q[i - 1] = each non-last output
                 for i in run:
                     self.dz8q[i] = torch.zeros(self.B * FP8_PITCH * self.plans[i].cout,
                                                dtype=torch.uint8, device=self.device)
-                y8 = [self.dz8q[run[0]].data_ptr()] + [
-                    self.dz8q[i - 1].data_ptr() if i != run[-1] else 0 for i in run]
                 # dz8q[j] that are exactly the bf16 frame dz[j] (the copy-out bytes)
                 self._dz8_exact = {i - 1 for i in run if i != run[-1]}
-                self._dstack_y8 = np.ascontiguousarray(np.array(y8, dtype=np.int64))
-                self._bwd_pre.append((self.h.conv_stack_f8_dgrad,
-                                      args + (self._dstack_y8.ctypes.data, sr)))
-            else:
-                self._bwd_pre.append((self.h.conv_stack_f8_dgrad, args + (0, sr)))
+                self._dstack_y8 = np.ascontiguousarray(np.array(
+                    [self.dz8q[top].data_ptr()] + [
+                        self.dz8q[i - 1].data_ptr() if i != run[-1] else 0 for i in run],
+                    dtype=np.int64))
+                y8 = self._dstack_y8.ctypes.data
+            self._bwd_pre.append(Op(self.h.conv_stack_f8_dgrad, (
+                self.plans[top].cout, self._dstack_table.ctypes.data, len(run),
+                self.dz[top].data_ptr(), self._s_g(top), self._gamax(top), self.B, y8,
+                self.step_count.data_ptr() if self.fp8_sr else 0), tuple(run)))
         else:
             rows = [[self.wdfrag[i].data_ptr(), 0, self.dz[i - 1].data_ptr(),
                      self.relu_mask[i - 1].data_ptr()] for i in run]
             self._dstack_table = np.ascontiguousarray(np.array(rows, dtype=np.int64))
-            self._bwd_pre.append((self.h.conv_stack2, (self.h.EPI_DGRAD,
-                                                      self._dstack_table.ctypes.data, len(run),
-                                                      self.dz[run[0]].data_ptr(), 0, self.B)))
-        self._dstack_run = run
-        for i in run:  # per-layer dgrad dropped: ops = [bias partial, wgrad, reduce]
-            self._bwd[i] = self._bwd[i][:3]
+            self._bwd_pre.append(Op(self.h.conv_stack2, (
+                self.h.EPI_DGRAD, self._dstack_table.ctypes.data, len(run),
+                self.dz[top].data_ptr(), 0, self.B), tuple(run)))
+        for i in run:  # the stack computes their dZ: no per-layer dgrad
+            self._bwd[i].dgrad = []
         # the remaining per-layer dgrads below the stack (layer 1 -> dZ_0) right after it, so
         # every dZ exists before the weight gradients (the first layer's chain can then run
         # beside the grouped launch)
-        if (os.environ.get("DG_DGRAD_FIRST", "1") != "0" and self.side_mode in ("none", "bias")
-                and all(len(self._bwd[i]) <= 3 or i == run[-1] - 1
-                        for i in range(1, run[-1]))):
-            for i in range(run[-1] - 1, 0, -1):
-                if len(self._bwd[i]) > 3:
-                    self._pre_dgrads[i] = self._bwd[i][3:]
-                    self._bwd_pre.extend(self._bwd[i][3:])
-                    self._bwd[i] = self._bwd[i][:3]
+        if self.knobs.DGRAD_FIRST and all(not self._bwd[i].dgrad or i == run[-1] - 1
+                                          for i in range(1, run[-1])):
+            self._dgrads_to_pre(range(run[-1] - 1, 0, -1))
             self._dgrad_first = True
-        self._group_wgrads(set([run[0]] + [i - 1 for i in run]))
+        self._group_wgrads(set([top] + [i - 1 for i in run]))
+
+    def _dgrads_to_pre(self, layers) -> bool:
+        """Move the per-layer dgrad launches of ``layers`` (top to bottom) into _bwd_pre,
+        in front of every weight gradient; whether there were any."""
+        n0 = len(self._bwd_pre)
+        for i in layers:
+            self._bwd_pre.extend(self._bwd[i].dgrad)
+            self._bwd[i].dgrad = []
+        return len(self._bwd_pre) > n0
 
     def _dgrads_first(self):
         """No board-resident dgrad stack for this shape (e.g. 256 channels): still run the
@@ -869,18 +914,7 @@ class HipGoNet:
         after the head — so every dZ exists before the weight gradients and those can run
         as grouped launches (fewer split-K partials).  DG_DGRAD_FIRST=0 keeps the
         interleaved per-layer order."""
-        if (os.environ.get("DG_DGRAD_FIRST", "1") == "0"
-                or self.side_mode not in ("none", "bias")):
-            return
-        moved = []
-        for i in range(len(self.plans) - 1, 0, -1):
-            ops = self._bwd[i]
-            if len(ops) > 3:
-                self._pre_dgrads[i] = ops[3:]
-                self._bwd_pre.extend(ops[3:])
-                self._bwd[i] = ops[:3]
-                moved.append(i)
-        if moved:
+        if self.knobs.DGRAD_FIRST and self._dgrads_to_pre(range(len(self.plans) - 1, 0, -1)):
             self._dgrad_first = True
             self._group_wgrads(set(range(len(self.plans))))
 
@@ -891,7 +925,7 @@ class HipGoNet:
         lay = self.layout.layers
         return (p.index > 0 and not p.fp8 and p.board and p.k == 3 and p.cin == p.cout == 256
                 and lay[p.index].pad == 1 and lay[p.index + 1].pad == 1
-                and os.environ.get("DG_LAYER2", "1") != "0")
+                and self.knobs.LAYER2)
 
     def _stack_l1_ok(self, p: ConvPlan) -> bool:
         """The first layer can run inside the bf16 forward stack's launch (conv_stack2.hip l1
@@ -900,8 +934,7 @@ class HipGoNet:
         lay = self.layout.layers
         return (p.index == 0 and not self.fp8 and p.k == 5 and p.cinp == 40 and p.cout == 128
                 and p.KP == 1024 and lay[0].pad == 2 and len(lay) > 2 and lay[1].pad == 1
-                and os.environ.get("DG_STACK_L1", "1") != "0"
-                and os.environ.get("DG_STACK", "1") != "0" and self._l1_res_ok(p))
+                and self.knobs.STACK_L1 and self.knobs.STACK and self._l1_res_ok(p))
 
     def _l1_frag_ok(self, p: ConvPlan) -> bool:
         """The 5x5 / 40-channel first layer on conv_l1_frag (conv_l1.hip: board per
@@ -909,7 +942,7 @@ class HipGoNet:
         stack does not absorb it (d = 256, fp8 models).  DG_L1_FRAG=0: conv_l1."""
         lay = self.layout.layers
         return (p.index == 0 and p.KP == 1024 and len(lay) > 2 and self._l1_res_ok(p)
-                and os.environ.get("DG_L1_FRAG", "1") != "0"
+                and self.knobs.L1_FRAG
                 and bool(self.h.conv_l1_frag_ok(p.k, lay[0].pad, p.cinp, p.cout, lay[1].pad)))
 
     def _l1_res_ok(self, p: ConvPlan) -> bool:
@@ -917,10 +950,6 @@ class HipGoNet:
         pass; otherwise the pixel-tiled implicit GEMM (conv_nt_ex)."""
         return (p.index == 0 and not p.board and not p.fp8
                 and bool(self.h.conv_l1_ok(p.k, self.layout.layers[0].pad, p.cinp, p.Mpad, p.KP)))
-
-    @staticmethod
-    def _noop(*_):
-        pass
 
     def _group_wgrads(self, dz_ready):
         """Weight gradients of up to DG_WGRAD_GROUP consecutive same-shape layers whose dZ
@@ -935,13 +964,9 @@ class HipGoNet:
         that a comm-stream kernel does NOT co-schedule with these full-machine launches
         (every CU's VGPR file is full: bench.py --force-dp --comm proxy, 0% overlap,
         profiles/r2_comm_overlap_proxy.txt), so the split only costs."""
-        self.wgroups: List[List[int]] = []
-        self.win_groups = set()
-        self.win8_groups = set()
-        self._l0_side_at = None
-        G = self._wgrad_group or int(os.environ.get("DG_WGRAD_GROUP", "16"))
+        G = self._wgrad_group or self.knobs.WGRAD_GROUP
         G = min(G, 16)                # MAXWL / RD_MAXL / BG_MAXL of the multi-layer kernels
-        if G < 2 or self.side_mode not in ("none", "bias"):
+        if G < 2:
             return
         lay = self.layout.layers
         h = self.h
@@ -987,7 +1012,7 @@ class HipGoNet:
         wgs = h.conv_wgrad_wgs_per_cu_for(self.plans[groups[0][0]].KPw)
         gslab_elems = 0
         plan_splits = {}
-        win_ok = os.environ.get("DG_WGRAD_WIN", "1") != "0"
+        win_ok = self.knobs.WGRAD_WIN
         for g in groups:
             p = self.plans[g[0]]
             if (win_ok and p.k == 3 and lay[g[0]].pad == 1 and self.dzp[g[0]] == 1
@@ -1004,11 +1029,9 @@ class HipGoNet:
                     S = h.conv_wgrad_win8_splits(len(g), p.cout, p.cinp, self.B, self.num_cus)
                 else:
                     S = h.conv_wgrad_win_splits(len(g), p.cout, p.cinp, self.B, self.num_cus)
-                plan_splits[tuple(g)] = S
-                gslab_elems = max(gslab_elems, len(g) * S * p.Mpad_w * p.KPw)
-                continue
-            tiles = (p.KPw // 384) * (p.Mpad_w // 128) * len(g)
-            S = max(1, min((self.num_cus * wgs) // tiles, self.npix // 256))
+            else:
+                tiles = (p.KPw // 384) * (p.Mpad_w // 128) * len(g)
+                S = max(1, min((self.num_cus * wgs) // tiles, self.npix // 256))
             plan_splits[tuple(g)] = S
             gslab_elems = max(gslab_elems, len(g) * S * p.Mpad_w * p.KPw)
         self.gslab = torch.empty(gslab_elems, dtype=torch.float32, device=self.device)
@@ -1031,15 +1054,13 @@ class HipGoNet:
                 spec = lay[i]
                 if w8:   # fp8 copies + their scales: gradient s_g[i], input s_y[i - 1]
                     wrows.append([self.dz8q[i].data_ptr(), self.x8q[i].data_ptr(), slab,
-                                  self.fp8_gscales.data_ptr() + 4 * i,
-                                  self.fp8_scales.data_ptr() + 4 * (2 * (i - 1) + 1)])
+                                  self._s_g(i), self._s_y(i - 1)])
                 else:
                     wrows.append([self.dz[i].data_ptr(), xin.data_ptr(), slab])
                 # bias partials: from the e5m2 copy where it is exactly the bf16 frame (the
                 # fp8 backward-data stack's copy-out; not its top input, which it rounds)
                 if w8 and i in self._dz8_exact:
-                    brows.append([self.dz8q[i].data_ptr(), bpart,
-                                  self.fp8_gscales.data_ptr() + 4 * i])
+                    brows.append([self.dz8q[i].data_ptr(), bpart, self._s_g(i)])
                 else:
                     brows.append([self.dz[i].data_ptr(), bpart, 0])
                 rrows.append([slab, G_ + spec.w_off * f4, bpart, G_ + spec.pos_off * f4,
@@ -1049,44 +1070,54 @@ class HipGoNet:
                                  self._g16(spec.b_off)] if self.grads16 is not None else []))
                 self.plans[i].splits = S
                 self._red_src[i] = (slab, bpart, S, p0.Mpad_w, p0.KPw, self.bchunks_g)
-                # ops = [bias partial, wgrad, reduce, (dgrad)]: the group's first layer
-                # launches all three passes for the whole group
-                self._bwd[i][0:3] = [(self._noop, ())] * 3
+                # the group's first layer launches all three passes for the whole group
+                self._bwd[i].bias = self._bwd[i].wgrad = self._bwd[i].reduce = None
             # layer 0's bias partials as one more row of the last group's launch (its chain
             # runs on the side stream right after it) at d = 128: 12x128 fp8 +1.1%, bf16
             # equal; at d = 256 the 5x5 weight gradient then starts earlier beside the window
             # kernel and stretches it (12x256 fp8 -6.6%, bf16 equal;
             # profiles/r4_s2_l0_bias_merge_ab.txt)
-            p_l0 = self.plans[0]
             if (g is groups[-1] and self._l0_side_at is not None and len(brows) < 16
-                    and p_l0.cout == p0.cout and p0.cout <= 128
-                    and self.dzp[0] == self.dzp[g[0]]
-                    and self._bwd[0][0][0] is h.bias_grad_partial_multi):
-                brows.append([self.dz[0].data_ptr(), self.bparts[0].data_ptr(), 0])
-                self._bwd[0][0] = (self._noop, ())
-            tabs = [np.ascontiguousarray(np.array(r, dtype=np.int64))
-                    for r in (wrows, brows, rrows)]
+                    and self.plans[0].cout == p0.cout and p0.cout <= 128
+                    and self.dzp[0] == self.dzp[g[0]] and self._bwd[0].bias is not None
+                    and self._bwd[0].bias.fn is h.bias_grad_partial_multi):
+                brows.append([self.dz[0].data_ptr(), self.bpart.data_ptr(), 0])
+                self._bwd[0].bias = None
+            wt, bt, rt = tabs = [np.ascontiguousarray(np.array(r, dtype=np.int64))
+                                 for r in (wrows, brows, rrows)]
             self._wgroup_tables.extend(tabs)
-            wt, bt, rt = tabs
-            self._bwd[g[0]][0:3] = [
-                (h.bias_grad_partial_multi, (bt.ctypes.data, len(bt), self.B, p0.cout,
-                                             self.dzp[g[0]], self._sf)),
-                (h.conv_wgrad_win8 if w8 else h.conv_wgrad_win,
-                 (wt.ctypes.data, len(g), p0.cout, p0.Mpad_w, p0.cinp, self.B, p0.KPw, S,
-                  self._sf))
-                if tuple(g) in self.win_groups else
-                (h.conv_wgrad_multi, (p0.k, wt.ctypes.data, len(g), self.dzp[g[0]],
-                                      p0.cout, p0.Mpad_w, spec0.pad, p0.cinp, self.B, p0.KPw,
-                                      S)),
-                (h.wgrad_reduce_multi_w if self.grads16 is not None else h.wgrad_reduce_multi,
-                 (rt.ctypes.data, len(rt))),
-            ]
+            b = self._bwd[g[0]]
+            b.bias = Op(h.bias_grad_partial_multi, (bt.ctypes.data, len(bt), self.B, p0.cout,
+                                                    self.dzp[g[0]], self._sf), tuple(g))
+            if tuple(g) in self.win_groups:
+                b.wgrad = Op(h.conv_wgrad_win8 if w8 else h.conv_wgrad_win, (
+                    wt.ctypes.data, len(g), p0.cout, p0.Mpad_w, p0.cinp, self.B, p0.KPw, S,
+                    self._sf), tuple(g))
+            else:
+                b.wgrad = Op(h.conv_wgrad_multi, (
+                    p0.k, wt.ctypes.data, len(g), self.dzp[g[0]], p0.cout, p0.Mpad_w, spec0.pad,
+                    p0.cinp, self.B, p0.KPw, S), tuple(g))
+            b.reduce = Op(
+                h.wgrad_reduce_multi_w if self.grads16 is not None else h.wgrad_reduce_multi,
+                (rt.ctypes.data, len(rt)), tuple(g))
 
     # ------------------------------------------------------------------ execution
+    # the launches outside the per-layer backward (_bwd): lists of ops, or one op / None
+    _OP_ATTRS = ("_pre", "_pre_train", "_fwd", "_fwd_train", "_head_train", "_head_eval",
+                 "_head_red", "_bwd_pre")
+
+    def _iter_ops(self) -> Iterator[Op]:
+        """Every launch forward(), forward_backward(), evaluate(), backward_layer() can issue."""
+        for n in self._OP_ATTRS:
+            v = getattr(self, n)
+            yield from (op for op in (v if isinstance(v, list) else [v]) if op is not None)
+        for b in self._bwd:
+            yield from b.ops()
+
     def _run(self, ops, s):
-        for f, a in ops:
-            f(*a, s)
-            if f is not HipGoNet._noop:
+        for op in ops:
+            if op is not None:       # (a launch that does not exist in this plan)
+                op.fn(*op.args, s)
                 self.launches += 1
 
     # ------------------------------------------------------------------ input prefetch
@@ -1111,17 +1142,15 @@ class HipGoNet:
         v1[2].fill_(1)
         m = {a.data_ptr(): b.data_ptr() for a, b in zip(v0, v1)}
 
-        def sub(op):
-            f, a = op
-            return (f, tuple(m.get(x, x) if type(x) is int else x for x in a))
-        names = ("_pre", "_pre_train", "_fwd", "_fwd_train")
-        ops0 = {n: list(getattr(self, n)) for n in names}
-        ops0["_head_train"] = self._head_train
-        ops0["_head_eval"] = self._head_eval
-        ops1 = {n: [sub(op) for op in ops0[n]] for n in names}
-        ops1["_head_train"] = sub(self._head_train)
-        ops1["_head_eval"] = sub(self._head_eval)
-        self._in_ops = [ops0, ops1]
+        def sub(v):
+            if isinstance(v, list):
+                return [sub(op) for op in v]
+            return v and dataclasses.replace(v, args=tuple(
+                m.get(x, x) if type(x) is int else x for x in v.args))
+        # (the per-layer backward reads no step input: its ops are shared by both sets)
+        assert not any(x in m for b in self._bwd for op in b.ops() for x in op.args)
+        ops0 = {n: getattr(self, n) for n in self._OP_ATTRS}
+        self._in_ops = [ops0, {n: sub(v) for n, v in ops0.items()}]
         self._in_views = [v0, v1]
         self._inbufs = [self.inbuf, buf1]
         self.load_stream = torch.cuda.Stream(device=self.device)
@@ -1241,15 +1270,14 @@ class HipGoNet:
         so with a side stream the weight-gradient chain runs beside the dgrad chain — the
         critical path is the dgrad sequence, and each kernel's ramp/tail is filled by the
         other stream's work.  Callers end the backward with ``join_side()``."""
-        ops = self._layer_ops(i)
+        b = self._layer_ops(i)
         main = torch.cuda.current_stream()
         if self.side_mode == "none":
-            self._run(ops[:3], main.cuda_stream)
-            for fn in hooks:
-                fn()
-        elif self.side_mode == "bias":
+            self._run([b.bias, b.wgrad, b.reduce], main.cuda_stream)
+        else:
             side = self.side
-            l0_side = self._l0_side_at == i
+            # layer 0's whole chain runs here, on the side stream, joined at layer 0
+            b0 = self._layer_ops(0) if self._l0_side_at == i else None
             sc = self.sc
             if i == 0 and self._l0_side_at is not None:
                 if sc:
@@ -1265,22 +1293,20 @@ class HipGoNet:
                     sc.consume("dz->side", side)
                 self._flush_head_reduce(side.cuda_stream)
                 self._issue_loss_gate(side.cuda_stream)
-                self._run(ops[:1], side.cuda_stream)
-                l0 = self._l0_dgrad + self._layer_ops(0)[:3] if l0_side else None
-                if l0_side and self._defer:
-                    # layer 0's bias partial (where it is a launch of its own: d = 256) and
-                    # what produces its dZ_0 BEFORE the event the early update waits on: the
+                self._run([b.bias], side.cuda_stream)
+                l0 = [b0.bias, b0.wgrad, b0.reduce] if b0 is not None else []
+                if b0 is not None and self._defer:
+                    # layer 0's bias partial (where it is a launch of its own: d = 256)
+                    # BEFORE the event the early update waits on: the
                     # partial's |dZ_0| check is a step-tag producer, and the early update must
                     # read the tag only after every producer (all-or-nothing).  The
                     # 5x5 slab reduce after it cannot trip on its own: |dZ_0| < 2^100 and
                     # x0 in {0, 1} bound the 5x5 gradient below the reduce's 2^120
-                    k = len(self._l0_dgrad) + 1
-                    self._run(l0[:k], side.cuda_stream)
-                    l0 = l0[k:]
+                    self._run([l0.pop(0)], side.cuda_stream)
                 ev = side.record_event()         # partials ready for the reduce
                 if sc:
                     sc.produce("partials->reduce", side)
-                # then dZ_0 and the first layer's whole chain, joined at layer 0.  Measured
+                # then the first layer's whole chain, joined at layer 0.  Measured
                 # (profiles/r3_l0_chain_stream_ab.txt): the chain before the partials, or on a
                 # third stream beside the grouped launch, is 5-6% slower at 12x128 and
                 # 0.3-1.6% at 12x256 — compute beside the window kernel slows it; and its
@@ -1288,18 +1314,17 @@ class HipGoNet:
                 # gradient then starts ~50 us earlier beside it) stretched the fp8 window
                 # kernel by 100 us: -6% at 12x256 fp8, 0 elsewhere
                 # (profiles/r4_s1_l0_bias_main_ab.txt)
-                if l0_side:
-                    self._run(l0, side.cuda_stream)
-                self._run(ops[1:2], main.cuda_stream)
+                self._run(l0, side.cuda_stream)
+                self._run([b.wgrad], main.cuda_stream)
                 main.wait_event(ev)
                 if sc:
                     sc.consume("partials->reduce", main)
-                self._run(ops[2:3], main.cuda_stream)
-                if l0_side:
+                self._run([b.reduce], main.cuda_stream)
+                if b0 is not None:
                     self._issue_early_update(main.cuda_stream)
-            for fn in hooks:
-                fn()
-        self._run(ops[3:], main.cuda_stream)
+        for fn in hooks:
+            fn()
+        self._run(b.dgrad, main.cuda_stream)
 
     def _issue_loss_gate(self, stream):
         """With the gradient pass 2 deferred the update's gate is the loss alone: issue it on
@@ -1307,19 +1332,19 @@ class HipGoNet:
         in front of the fused update."""
         if (self._defer and not self._gate_issued and self.cfg.nan_policy != "raise"
                 and self.grads16 is None):
-            self._run([(self.h.finite_gate, (self.loss.data_ptr(), self.B, 0, 0,
-                                             self.gate.data_ptr(), self.bad_steps.data_ptr()))],
+            self._run([Op(self.h.finite_gate, (self.loss.data_ptr(), self.B, 0, 0,
+                                               self.gate.data_ptr(), self.bad_steps.data_ptr()))],
                       stream)
             self._gate_issued = True
 
-    def _layer_ops(self, i: int):
-        """Layer i's backward ops [bias partial, wgrad, pass 2, (dgrad)]; with the step's
-        gradient pass 2 deferred into the fused update, the pass-2 launch (the slab reduce
-        that also finishes the bias gradients) is left out."""
-        ops = self._bwd[i]
-        if self._defer and len(ops) >= 3 and i in self._defer_layers():
-            ops = ops[:2] + [(self._noop, ())] + ops[3:]
-        return ops
+    def _layer_ops(self, i: int) -> LayerBwd:
+        """Layer i's backward launches; with the step's gradient pass 2 deferred into the fused
+        update, the pass-2 launch (the slab reduce that also finishes the bias gradients) is
+        left out."""
+        b = self._bwd[i]
+        if self._defer and i in self._defer_layers():
+            b = dataclasses.replace(b, reduce=None)
+        return b
 
     def _defer_layers(self) -> set:
         """Layers whose pass 2 the fused update takes over when deferred: the grouped
@@ -1338,7 +1363,7 @@ class HipGoNet:
         every layer's slabs / partials in buffers of their own: one grouped weight-gradient
         launch, plus at most the first layer's own chain.  DG_FUSED_UPDATE=0: never (and the
         optimizer keeps the separate SGD + refresh launches)."""
-        if os.environ.get("DG_FUSED_UPDATE", "1") == "0":
+        if not self.knobs.FUSED_UPDATE:
             return False
         if self.global_batch != self.B or self.grads16 is not None or self.grad_hooks:
             return False
@@ -1368,11 +1393,8 @@ class HipGoNet:
         return self.sc.check() if self.sc else 0
 
     def evaluate(self):
-        s = stream_handle()
-        self._run(self._pre, s)
-        self._run(self._fwd, s)
-        f, a = self._head_eval
-        f(*a, s)
+        self.forward()
+        self._head_eval.fn(*self._head_eval.args, stream_handle())
 
     def optimizer_step(self, grad_scale: float = 1.0):
         """The update: [finite gate] -> [fp8 scale update] -> ONE fused launch (grad_update:
@@ -1381,7 +1403,7 @@ class HipGoNet:
         SGD / RMSProp and weight-refresh launches."""
         s = stream_handle()
         n = self.layout.numel
-        gate = 0
+        gate = self.gate.data_ptr() if self.cfg.nan_policy != "raise" else 0
         slabs = self._defer
         # (bf16 wire: the optimizer reads the all-reduced bf16 twin)
         w16 = self.grads16 is not None
@@ -1397,13 +1419,10 @@ class HipGoNet:
                                 0 if (slabs or w16) else g, g if (w16 and not slabs) else 0,
                                 0 if slabs else n, self.gate.data_ptr(),
                                 self.bad_steps.data_ptr(), self._gate_ticket.data_ptr(), s)
-            gate = self.gate.data_ptr()
-        if self.cfg.nan_policy != "raise":
-            gate = self.gate.data_ptr()
         self._gate_issued = False
         if not (slabs and self._early_issued):
             self._fp8_update(s)
-        if os.environ.get("DG_FUSED_UPDATE", "1") == "0":
+        if not self.knobs.FUSED_UPDATE:
             if self.ms is not None:
                 (self.h.rmsprop_bf16 if w16 else self.h.rmsprop)(
                     self.params.data_ptr(), g, self.ms.data_ptr(), n, self.lr.data_ptr(),
@@ -1486,6 +1505,7 @@ class HipGoNet:
         t = getattr(self, key, None)
         if t is None:
             ref = self._step_refresh_table()
+            assert ref.shape[1] == GU_SLAB     # the source columns follow the refresh row
             rows = []
             for r, p in zip(ref, self.plans):
                 spec = self.layout.layers[p.index]
@@ -1499,22 +1519,9 @@ class HipGoNet:
         return t
 
     def _op_pointers(self, exclude=()) -> set:
-        """Every integer argument (and int64 table entry) of the launches the model issues:
-        the input / forward / head / backward op lists that forward(), forward_backward(),
-        evaluate() and backward_layer() run."""
-        vals = set()
-
-        def add(op):
-            f, a = op
-            for v in a:
-                if isinstance(v, int):
-                    vals.add(v)
-        for lst in (self._pre, self._fwd, self._fwd_train, self._bwd_pre,
-                    getattr(self, "_l0_dgrad", []), *self._bwd):
-            for op in lst:
-                add(op)
-        for op in (self._head_train, self._head_red, self._head_eval):
-            add(op)
+        """Every integer argument (and int64 table entry) of the launches the model issues
+        (_iter_ops)."""
+        vals = {v for op in self._iter_ops() for v in op.args if isinstance(v, int)}
         # every int64 launch table the model holds (stack / dgrad-stack / layer-run / grouped
         # weight-gradient / fp8 copy-out tables), except the refresh tables (operand copies
         # are what _step_refresh_table decides about) and any passed in `exclude`
@@ -1537,7 +1544,7 @@ class HipGoNet:
             used = self._op_pointers()
             t = self._refresh_table.copy()
             # wf, wd, wf8 (plain) and wf_frag, wd_frag, wf8_frag, wd8_frag (stack orders)
-            for col in (1, 2, 10, 16, 17, 18, 19):
+            for col in RT_WEIGHT_COPIES:
                 for r in range(len(t)):
                     if t[r, col] and int(t[r, col]) not in used:
                         t[r, col] = 0
@@ -1599,15 +1606,6 @@ class HipGoNet:
     def load_params(self, flat: torch.Tensor):
         self.params.copy_(flat.to(self.params.device, torch.float32))
         self.refresh_weights()
-
-    def state_tensors(self):
-        return {"params": self.params, "lr": self.lr, "step": self.step_count}
-
-    def memory_bytes(self) -> int:
-        uniq = {t.data_ptr(): t for t in (*self.slabs, *self.bparts)}
-        ts = [self.params, self.grads, *uniq.values(), self.x0, *self.act, *self.dz, *self.wf,
-              *[w for w in self.wd if w is not None]]
-        return sum(t.numel() * t.element_size() for t in ts)
 
 
 class SegmentedStep:

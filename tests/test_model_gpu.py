@@ -528,7 +528,7 @@ def test_head_fused_into_d256_forward(dtype, monkeypatch):
         n0.fp8_gscales.copy_(n1.fp8_gscales)
     want = n1.h.conv_stack_f8_fwd_head_y8 if dtype == "fp8" else n1.h.conv_layer2_multi_head
     assert any(f is want for f, _ in n1._fwd_train)
-    assert n1._head_train[0] is n1._noop and n0._head_train[0] is not n0._noop
+    assert n1._head_train is None and n0._head_train is not None
     n0.forward_backward()
     n1.forward_backward()
     torch.cuda.synchronize()
@@ -608,7 +608,6 @@ def test_fused_update_matches_separate_launches(layers, ch, dtype, opt, monkeypa
     # (d = 64: no grouped weight-gradient launch, so the step reduces first and the fused
     # launch reads the flat gradient — still one update launch)
     assert net1.can_defer() == (ch >= 128)
-    monkeypatch.setenv("DG_FUSED_UPDATE", "0")
     assert not net0.can_defer()
 
     def copies(n):
@@ -633,19 +632,12 @@ def test_fused_update_matches_separate_launches(layers, ch, dtype, opt, monkeypa
             assert torch.equal(net0.fp8_scales, net1.fp8_scales)
         assert int(net1.gu_tickets.abs().sum().item()) == 0    # tickets left zeroed
     for _ in range(3):
-        monkeypatch.setenv("DG_FUSED_UPDATE", "0")
         net0.train_step()
-        monkeypatch.setenv("DG_FUSED_UPDATE", "1")
         net1.train_step()
     check()
-    steps = []
-    for fused, net in (("0", net0), ("1", net1)):
-        monkeypatch.setenv("DG_FUSED_UPDATE", fused)
-        steps.append(SegmentedStep(net, None, use_graphs=True))
+    steps = [SegmentedStep(net, None, use_graphs=True) for net in (net0, net1)]
     for _ in range(2):
-        monkeypatch.setenv("DG_FUSED_UPDATE", "0")
         steps[0]()
-        monkeypatch.setenv("DG_FUSED_UPDATE", "1")
         steps[1]()
     check()
 

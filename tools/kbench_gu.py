@@ -21,15 +21,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-# refresh-row columns that hold optional operand-copy outputs (elementwise.hip
-# parse_refresh_row): wf, wd, pbias_frag, wf8, pbias, wf_frag, wd_frag, wf8_frag, wd8_frag
-COPY_COLS = (1, 2, 9, 10, 15, 16, 17, 18, 19)
-
-
 def main():
     from deep_go_amd.config import get_preset
     from deep_go_amd.data.synthetic import random_planes
-    from deep_go_amd.models.hip_model import HipGoNet
+    from deep_go_amd.models.hip_model import (GU_BPART, GU_SLAB, GU_SPLITS, RT_PBIAS,
+                                              RT_PBIAS_FRAG, RT_WEIGHT_COPIES, HipGoNet)
     from deep_go_amd.ops.native import stream_handle
     ch = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     dt = sys.argv[2] if len(sys.argv) > 2 else "bf16"
@@ -62,22 +58,23 @@ def main():
 
     variants = {"full": base}
     t = base.copy()
-    sl = t[:, 20] != 0
-    t[sl, 22] = 1
+    sl = t[:, GU_SLAB] != 0
+    t[sl, GU_SPLITS] = 1
     variants["splits1"] = t
     t = base.copy()
-    t[:, 21] = 0
+    t[:, GU_BPART] = 0
     variants["nobias"] = t
     t = base.copy()
-    t[:, list(COPY_COLS)] = 0
+    # every refresh-row column that holds an optional operand-copy output
+    t[:, [*RT_WEIGHT_COPIES, RT_PBIAS_FRAG, RT_PBIAS]] = 0
     variants["nocopy"] = t
     variants["noslab"] = flat
     runs = {k: gu(np.ascontiguousarray(v)) for k, v in variants.items()}
 
     def old():
         for g in net.wgroups:              # the grouped slab reduce(s) the deferral skips
-            f, a = net._bwd[g[0]][2]
-            f(*a, s)
+            red = net._bwd[g[0]].reduce
+            red.fn(*red.args, s)
         h.sgd(net.params.data_ptr(), net.grads.data_ptr(), n, net.lr.data_ptr(), 1.0,
               net.gate.data_ptr(), s)
         rt = net._step_refresh_table()

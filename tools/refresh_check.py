@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from deep_go_amd.config import get_preset  # noqa: E402
-from deep_go_amd.models.hip_model import HipGoNet  # noqa: E402
+from deep_go_amd.models.hip_model import RT_WEIGHT_COPIES, HipGoNet  # noqa: E402
 
 
 def main():
@@ -15,8 +15,7 @@ def main():
         cfg = get_preset("12x128-bf16", numLayers=12, channelSize=ch, batchSize=256, dtype=dt)
         net = HipGoNet(cfg, 256, device="cuda")
         full, step = net._refresh_table, net._step_refresh_table()
-        names = {1: "wf", 2: "wd", 10: "wf8", 16: "wf_frag", 17: "wd_frag", 18: "wf8_frag",
-                 19: "wd8_frag"}
+        names = RT_WEIGHT_COPIES
         for i in range(len(full)):
             kept = [n for c, n in names.items() if step[i, c]]
             dropped = [n for c, n in names.items() if full[i, c] and not step[i, c]]
