@@ -150,6 +150,14 @@ hipError_t dg_grad_update(const long long* table, int n, long long plain_off, lo
                           float gscale, const float* gate, double* lr, double decay,
                           long long* step, unsigned* tickets, int* bad_steps, int write_grads, int final,
                           const long long* gflag, hipStream_t s);
+hipError_t dg_symmetry_planes(const uint8_t* src_planes, const uint8_t* src_player,
+                              const uint8_t* src_rank, const int* src_labels, int n, int S,
+                              uint8_t* planes, uint8_t* player, uint8_t* rank, int* labels,
+                              int B, hipStream_t s);
+hipError_t dg_policy_ensemble(const float* logp, const uint8_t* stones, int stones_stride,
+                              const uint8_t* extra_illegal, const int* labels, int n, int S,
+                              int K, int mask, float* prob, int* topk_idx, float* topk_p,
+                              int* label_rank, hipStream_t s);
 }
 
 namespace {
@@ -430,6 +438,26 @@ PYBIND11_MODULE(_dghip, m) {
                              P<void>(out), B, pad, CP, nullptr, 0, S(stream)),
           "expand_features");
   });
+  m.def("symmetry_planes", [](uintptr_t src_planes, uintptr_t src_player, uintptr_t src_rank,
+                              uintptr_t src_labels, int n, int nsym, uintptr_t planes,
+                              uintptr_t player, uintptr_t rank, uintptr_t labels, int B,
+                              uintptr_t stream) {
+    check(dg_symmetry_planes(P<uint8_t>(src_planes), P<uint8_t>(src_player),
+                             P<uint8_t>(src_rank), P<int>(src_labels), n, nsym, P<uint8_t>(planes),
+                             P<uint8_t>(player), P<uint8_t>(rank), P<int>(labels), B, S(stream)),
+          "symmetry_planes");
+  }, "boards i S + s of a packed batch of capacity B <- source board i moved by symmetry s "
+     "(policy.hip)");
+  m.def("policy_ensemble", [](uintptr_t logp, uintptr_t stones, int stones_stride,
+                              uintptr_t extra_illegal, uintptr_t labels, int n, int nsym, int K,
+                              int mask, uintptr_t prob, uintptr_t topk_idx, uintptr_t topk_p,
+                              uintptr_t label_rank, uintptr_t stream) {
+    check(dg_policy_ensemble(P<float>(logp), P<uint8_t>(stones), stones_stride,
+                             P<uint8_t>(extra_illegal), P<int>(labels), n, nsym, K, mask,
+                             P<float>(prob), P<int>(topk_idx), P<float>(topk_p),
+                             P<int>(label_rank), S(stream)),
+          "policy_ensemble");
+  }, "symmetry-averaged, legality-masked policy with top-k and label rank (policy.hip)");
   m.def("bias_grad_partial", [](uintptr_t dZ, int B, int C, int pad, uintptr_t part,
                                 uintptr_t stream) {
     check(dg_bias_grad_partial(P<void>(dZ), B, C, pad, P<float>(part), S(stream)),

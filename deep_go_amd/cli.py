@@ -4,7 +4,11 @@
             (localtest.lua / default-experiment.lua / notebook equivalents via presets)
   resume    CKPT --iters N [--reset-optimizer] [--id NAME] [key=value ...]
             (experiments/repeated.lua: -gpu/-num/-iters -> --device/--id/--iters)
-  eval      CKPT [--split test] [--n N]          (top-1 / NLL on a split; never done in the ref)
+  eval      CKPT [--split test] [--n N] [--symmetries 8] [--top K]
+            (top-1 / NLL on a split; never done in the ref.  With --symmetries / --top also the
+            symmetry-ensembled, legality-masked top-k accuracy and mean rank: deep_go_amd.predict)
+  predict   CKPT GAME.sgf [--move N] [--top K] [--symmetries {1,8}] [--device auto|cpu|gpu] [--all]
+            (where to play and with what probability: one JSON line per requested move)
   makedata  scatter SRC DST train=N validation=N test=N | transcribe SRC DST [--threads T] [--ko]
             | count ROOT SPLIT | pack ROOT SPLIT
   export    CKPT OUT.t7        (reference Torch7 experiment table)
@@ -91,11 +95,61 @@ def cmd_eval(args):
     e = Experiment.load(args.checkpoint)
     if args.device == "cpu":
         e.cfg = e.cfg.replace(useCuda=False)
+    extra = {}
     try:
         cost, acc = e.evaluate_split(args.split, args.n)
+        if args.symmetries is not None or args.top is not None:
+            extra = _eval_ensemble(e, args)
     finally:
         e.close()
-    print(json.dumps({"split": args.split, "cost": cost, "accuracy": acc}))
+    print(json.dumps({"split": args.split, "cost": cost, "accuracy": acc, **extra}))
+    return 0
+
+
+def _eval_ensemble(e, args):
+    """eval --symmetries / --top: the same sample set through the Predictor (symmetry
+    ensemble, occupied points masked): top-k accuracy, mean rank of the expert move, top-1."""
+    import numpy as np
+    from .predict import Predictor
+    S, K = args.symmetries or 8, args.top or 5
+    planes, player, rank, labels = e.draw_validation(args.n or e.cfg.validationSize,
+                                                     split=args.split, seed_offset=99)
+    p = Predictor(e.cfg, e.backend.flat_params(), batch=64, symmetries=S, top=K,
+                  device="cpu" if e._device_kind() == "cpu" else "gpu")
+    r = p.predict(planes, player, rank, labels=labels).rank
+    ok = r >= 0    # (a label on an occupied point has no rank: counted as a miss)
+    return {"symmetries": S, "top": K,
+            "topk_accuracy": float(np.mean(ok & (r < K))),
+            "mean_rank": float(r[ok].mean()) if ok.any() else None,
+            "ensemble_accuracy": float(np.mean(r == 0))}
+
+
+def _sgf_point(p: int):
+    x, y = divmod(int(p), 19)
+    return {"sgf": chr(ord("a") + x) + chr(ord("a") + y), "x": x, "y": y}
+
+
+def cmd_predict(args):
+    from .predict import Predictor, ko_mask, positions_from_sgf
+    p = Predictor.load(args.checkpoint, symmetries=args.symmetries, top=args.top,
+                       device=args.device, batch=64)
+    with open(args.sgf, newline="") as f:
+        text = f.read()
+    planes, player, rank, label, ko = positions_from_sgf(text, mark_ko=p.cfg.ko_plane)
+    n = len(label)
+    if n == 0:
+        raise SystemExit(f"{args.sgf}: no moves")
+    move = n if args.move is None else args.move
+    if not 1 <= move <= n:
+        raise SystemExit(f"--move {move}: the game has moves 1..{n}")
+    sel = slice(0, n) if args.all else slice(move - 1, move)
+    r = p.predict(planes[sel], player[sel], rank[sel], labels=label[sel],
+                  extra_illegal=ko_mask(ko[sel]))
+    for k, m in enumerate(range(sel.start, sel.stop)):
+        top = [dict(_sgf_point(q), p=float(pr)) for q, pr in zip(r.topk[k], r.topk_p[k])
+               if q >= 0]
+        print(json.dumps({"move": m + 1, "player": "B" if player[m] == 1 else "W", "top": top,
+                          "played": _sgf_point(label[m]), "rank": int(r.rank[k])}))
     return 0
 
 
@@ -177,7 +231,19 @@ def main(argv=None):
     e.add_argument("--split", default="test")
     e.add_argument("--n", type=int)
     e.add_argument("--device", choices=["auto", "cpu", "gpu"], default="auto")
+    e.add_argument("--symmetries", type=int, choices=[1, 8],
+                   help="also report the symmetry-ensembled top-k accuracy / mean rank")
+    e.add_argument("--top", type=int, help="k of topk_accuracy (default 5)")
     e.set_defaults(fn=cmd_eval)
+    q = sub.add_parser("predict")
+    q.add_argument("checkpoint")
+    q.add_argument("sgf")
+    q.add_argument("--move", type=int, help="1-based move number (default: the last move)")
+    q.add_argument("--top", type=int, default=5)
+    q.add_argument("--symmetries", type=int, choices=[1, 8], default=8)
+    q.add_argument("--device", choices=["auto", "cpu", "gpu"], default="auto")
+    q.add_argument("--all", action="store_true", help="every move of the game")
+    q.set_defaults(fn=cmd_predict)
     m = sub.add_parser("makedata")
     m.add_argument("--threads", type=int, default=32)
     m.add_argument("--ko", action="store_true",

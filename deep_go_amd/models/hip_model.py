@@ -1396,6 +1396,39 @@ class HipGoNet:
         self.forward()
         self._head_eval.fn(*self._head_eval.args, stream_handle())
 
+    # ------------------------------------------------------------------ prediction
+    # the log-probabilities of the whole batch, for deep_go_amd.predict: allocated and planned
+    # on demand (enable_predict), never part of a training step
+    logp: Optional[torch.Tensor] = None
+    _head_predict: Optional[Op] = None
+    _head_predict_in: Optional[int] = None    # the input buffer (cur_in) it was built for
+    _HEAD_LOGP_ARG = 11                        # position of logp_out in the head's arguments
+
+    def enable_predict(self) -> torch.Tensor:
+        """Allocate ``self.logp`` [B, 361] fp32 and build the forward-only head launch that
+        writes it: the evaluation head with the log-probability output filled in.  With input
+        prefetch enabled the launch reads the labels of the input buffer ``select_inputs``
+        currently points at; ``predict_logp`` rebuilds it when that buffer has changed."""
+        if self.logp is None:
+            self.logp = torch.zeros((self.B, NUM_POINTS), dtype=torch.float32,
+                                    device=self.device)
+        ev = self._head_eval     # (of the current input buffer: select_inputs swaps it)
+        k = self._HEAD_LOGP_ARG
+        if ev.fn is not self.h.head or ev.args[k] != 0:
+            raise RuntimeError("enable_predict: unexpected evaluation head launch")
+        self._head_predict = Op(ev.fn, ev.args[:k] + (self.logp.data_ptr(),) + ev.args[k + 1:])
+        self._head_predict_in = self.cur_in
+        return self.logp
+
+    def predict_logp(self) -> torch.Tensor:
+        """Forward pass on the current inputs; returns ``self.logp`` [B, 361], the head's
+        log-probabilities (the launches of ``evaluate()``, on the current stream)."""
+        if self._head_predict is None or self._head_predict_in != self.cur_in:
+            self.enable_predict()
+        self.forward()
+        self._run([self._head_predict], stream_handle())
+        return self.logp
+
     def optimizer_step(self, grad_scale: float = 1.0):
         """The update: [finite gate] -> [fp8 scale update] -> ONE fused launch (grad_update:
         the gradient's pass 2 when the step deferred it, SGD / RMSProp on every parameter,

@@ -353,3 +353,55 @@ def weight_refresh(w: torch.Tensor, cinp: int, KP: int, Mpad: int, KPd: int = 0,
     if frag:
         return wf, wd, ff, fd
     return wf, wd
+
+
+def symmetry_planes(planes: torch.Tensor, player: torch.Tensor, rank: torch.Tensor,
+                    labels: torch.Tensor, S: int = 8, B: int | None = None,
+                    out: torch.Tensor | None = None):
+    """Stored positions [n,9,19,19] uint8 -> a packed batch buffer (data/batch.py layout, B >=
+    n*S boards) whose board i*S + s is position i moved by symmetry s (data/symmetry.py), with
+    the same player / rank and the moved label.  Returns (buffer, its four views); ``out``: an
+    existing buffer of that capacity to write into (bytes outside boards < n*S stay)."""
+    from ..data.batch import packed_batch_bytes, unpack_views
+    h = hip()
+    dev = torch.device("cuda")
+    n = planes.shape[0]
+    B = n * S if B is None else B
+    pl = planes.to(dev, torch.uint8).reshape(n, 9, NPTS).contiguous()
+    py = player.to(dev, torch.uint8).contiguous()
+    rk = rank.to(dev, torch.uint8).contiguous()
+    lb = labels.to(dev, torch.int32).contiguous()
+    if out is None:
+        out = torch.zeros(packed_batch_bytes(B), dtype=torch.uint8, device=dev)
+    assert out.numel() == packed_batch_bytes(B) and out.dtype == torch.uint8
+    v = unpack_views(out, B)
+    h.symmetry_planes(pl.data_ptr(), py.data_ptr(), rk.data_ptr(), lb.data_ptr(), n, S,
+                      v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), B,
+                      stream_handle())
+    return out, v
+
+
+def policy_ensemble(logp: torch.Tensor, stones: torch.Tensor | None = None,
+                    extra_illegal: torch.Tensor | None = None,
+                    labels: torch.Tensor | None = None, S: int = 8, K: int = 5,
+                    mask: bool = True):
+    """logp [n*S,361] fp32 (row i*S + s: position i seen through symmetry s), stones [n,361]
+    uint8 of the untransformed positions (0 = empty) -> dict with prob [n,361], topk [n,K]
+    int32, topk_p [n,K] and rank [n] int32 (data/symmetry.py ensemble_policy is the oracle)."""
+    h = hip()
+    dev = torch.device("cuda")
+    lp = logp.to(dev, torch.float32).reshape(-1, NPTS).contiguous()
+    assert lp.shape[0] % S == 0
+    n = lp.shape[0] // S
+    st = stones.to(dev, torch.uint8).reshape(n, NPTS).contiguous() if stones is not None else None
+    ex = (extra_illegal.to(dev, torch.uint8).reshape(n, NPTS).contiguous()
+          if extra_illegal is not None else None)
+    lb = labels.to(dev, torch.int32).contiguous() if labels is not None else None
+    prob = torch.empty((n, NPTS), dtype=torch.float32, device=dev)
+    topk = torch.empty((n, K), dtype=torch.int32, device=dev)
+    topk_p = torch.empty((n, K), dtype=torch.float32, device=dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    h.policy_ensemble(lp.data_ptr(), _ptr(st), NPTS, _ptr(ex), _ptr(lb), n, S, K, int(mask),
+                      prob.data_ptr(), topk.data_ptr(), topk_p.data_ptr(), rank.data_ptr(),
+                      stream_handle())
+    return {"prob": prob, "topk": topk, "topk_p": topk_p, "rank": rank}
