@@ -17,6 +17,7 @@
 // Wave layout: WM x WN = 8 waves; each wave owns MF x NF 16x16 fragments
 // (v_mfma_f32_16x16x32_bf16): BM = 128 -> 2 x 4 waves, 4 x 6 fragments; BM = 64 -> 1 x 8
 // waves, 4 x 3 fragments.  N covers 384 >= 361 pixel columns (6% padding).
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -357,9 +358,6 @@ hipError_t dispatch_epi(int epi, const BoardArgs& a, int B, int Mpad, hipStream_
 static int g_board_ablate = 0;
 extern "C" void dg_conv_board_set_ablate(int mode) { g_board_ablate = mode; }
 
-// pbias (EPI_FWD, optional): bf16 [361][M] bias + pos_bias table (replaces bias / posb);
-// mask (optional): ReLU bitmask [B][361][M/8] — EPI_FWD writes it, EPI_DGRAD gates with it
-// instead of reading the aux activation frame.
 extern "C" hipError_t dg_conv_board_ex(int epi, int kw, int bm, const void* A, int KP, int M,
                                        int Mpad, const void* X, int x_pad, int x_C, int B,
                                        void* Y, int y_pad, const float* bias, const float* posb,

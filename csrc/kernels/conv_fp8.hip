@@ -18,6 +18,7 @@
 // per step.
 //
 // Reference op: nn.SpatialConvolutionMM forward + nn.Add + nn.ReLU (experiments.lua:138-147).
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;

@@ -16,6 +16,7 @@
 // SpatialConvolutionMM(37 -> d, 5x5), Add (per-position bias), ReLU).
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 #include "dg_features.h"
 
@@ -389,8 +390,6 @@ __global__ void __launch_bounds__(512, NFX == 6 ? 1 : 2) conv_l1_frag_kernel(L1F
 
 extern "C" {
 
-// Usable for: 3x3 / 5x5, pad (k-1)/2 input frame with x_C <= 64 channels (multiple of 8),
-// output channels padded to 128, K padded to 64 with zero weights.
 int dg_conv_l1_ok(int kw, int x_pad, int x_C, int Mpad, int KP) {
   if (!(kw == 3 || kw == 5) || x_pad != (kw - 1) / 2 || x_C % 8 != 0 || x_C > 64 ||
       Mpad % BM != 0 || KP % 64 != 0 || KP < kw * kw * x_C)
@@ -417,10 +416,6 @@ hipError_t dg_conv_l1(int kw, const void* A, int KP, int M, int Mpad, const void
   return w4 ? launch_l1<3, 4>(a, Mpad, stream) : launch_l1<3, 8>(a, Mpad, stream);
 }
 
-
-// conv_l1_frag: 5x5 over the [B][23][23][40] input frame -> [B][21][21][M] (pad 1), M a
-// multiple of 128; A = weight_refresh's fragment-ordered first-layer operand, pbias = its
-// stack-order bias table; mask optional.
 int dg_conv_l1_frag_ok(int kw, int x_pad, int x_C, int M, int y_pad) {
   return kw == 5 && x_pad == 2 && x_C == 40 && M % 128 == 0 && M <= 512 && y_pad == 1;
 }

@@ -16,6 +16,7 @@
 // ring with a barrier per K-step.
 // Reference ops: SpatialConvolutionMM + Add + ReLU (experiments.lua:137-147) and their
 // backward (train.lua:10).
+#include "dg_api.h"
 #include "dg_common.h"
 #include "head_body.h"
 
@@ -475,8 +476,6 @@ hipError_t launch_layer2_multi(const MultiArgs& m, int B, hipStream_t stream) {
 
 extern "C" {
 
-// epi 1: forward (pbias required, mask written if given); 2: backward-data (mask of the
-// layer below required).  C = 256 (128 works too: 2 chunks, one workgroup per board).
 hipError_t dg_conv_layer2(int epi, const void* A, const void* pbias, const void* X, void* Y,
                           void* mask, int C, int B, hipStream_t stream) {
   if ((C != 128 && C != 256) || B <= 0 || !A || !X || !Y) return hipErrorInvalidValue;
@@ -488,9 +487,8 @@ hipError_t dg_conv_layer2(int epi, const void* A, const void* pbias, const void*
   return hipErrorInvalidValue;
 }
 
-// nl layers in one launch: table = nl rows of {A, pbias, X, Y, mask} (int64); row l + 1's X
-// must be row l's Y (checked).  C = 256 | 128 as above.  head (forward, C = 256 only, or
-// null): the fused policy head on the last Y (head->X is set here).
+// dg_conv_layer2_multi and, with head (forward, C = 256 only, or null), _multi_head: the
+// fused policy head on the last Y (head->X is set here).
 static hipError_t layer2_multi(int epi, const long long* table, int nl, int C, int B,
                                const dghead::HeadMArgs* head, hipStream_t stream) {
   if ((C != 128 && C != 256) || B <= 0 || nl <= 0 || nl > MAXL2) return hipErrorInvalidValue;
@@ -523,7 +521,6 @@ hipError_t dg_conv_layer2_multi(int epi, const long long* table, int nl, int C, 
   return layer2_multi(epi, table, nl, C, B, nullptr, stream);
 }
 
-// the forward run + the fused policy head (3x3 / 256-channel head on the run's last output)
 hipError_t dg_conv_layer2_multi_head(const long long* table, int nl, int B, const float* w,
                                      const float* bias, const float* posb, const int* labels,
                                      float* loss, int* pred, void* dZ, float* gw_part,

@@ -22,6 +22,7 @@
 //    CDNA4 transposing LDS read ds_read_b64_tr_b16.
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -935,7 +936,6 @@ static hipError_t dispatch_tile(int epi, const ConvNTArgs& a, int Mpad, int bm, 
 
 extern "C" {
 
-// Conv (forward / dgrad / linear) via the NT implicit-GEMM kernel.
 hipError_t dg_conv_nt_ex(int epi, int kw, int bm, int bn, const void* A, int KP, int M,
                          int Mpad, const void* X, int x_pad, int x_C, int Npix, void* Y,
                          int y_pad, const float* bias, const float* posb, const void* aux,
@@ -980,18 +980,15 @@ hipError_t dg_conv_nt(int epi, int kw, int bm, int bn, const void* A, int KP, in
 
 static int g_wgrad_ablate = 0;
 void dg_conv_wgrad_set_ablate(int m) { g_wgrad_ablate = m; }
-// the 5x5 weight gradient's kernel: 4 = conv_wgrad_pipe_kernel with four 32-pixel stages
-// (default: 32.0 vs 32.9 us alone, +0.1..+0.7% in the four configurations' steps, 108 vs 165
-// VGPRs; five stages measured slower, 37 us: profiles/r6_wgrad5_pipe.txt), 0 =
-// conv_wgrad_kernel (two 64-pixel stages; bit-identical slabs).  DG_WGRAD5_NS=0 | 4
+// the 5x5 weight gradient's kernel (dg_conv_wgrad5_set_ns; DG_WGRAD5_NS=0 | 4).  Default 4:
+// 32.0 vs 32.9 us alone, +0.1..+0.7% in the four configurations' steps, 108 vs 165 VGPRs;
+// five stages measured slower, 37 us: profiles/r6_wgrad5_pipe.txt
 static int g_wgrad5_ns = [] {
   const char* e = getenv("DG_WGRAD5_NS");
   return e && atoi(e) == 0 ? 0 : 4;
 }();
 void dg_conv_wgrad5_set_ns(int ns) { g_wgrad5_ns = ns == 4 ? 4 : 0; }
 int dg_conv_wgrad_wgs_per_cu() { return 2; }
-// k-tile width / workgroups per CU of the kernel dg_conv_wgrad will use for this K: the
-// three-slice kernel wherever K is a multiple of 384
 int dg_conv_wgrad_ktile(int KP) { return KP % 384 == 0 ? 384 : 128; }
 int dg_conv_wgrad_wgs_per_cu_for(int KP) {
   return dg_conv_wgrad_ktile(KP) == 384 ? 1 : dg_conv_wgrad_wgs_per_cu();
@@ -1055,10 +1052,6 @@ hipError_t dg_conv_wgrad(int kw, const void* dZ, int dz_pad, int M, int Mpad, co
   return hipGetLastError();
 }
 
-// Weight gradients of nl layers of identical geometry in ONE launch (three-slice tiles):
-// table = nl rows of {dZ frame, X frame, slab} pointers; each layer gets `splits` pixel
-// splits.  Fewer splits per layer than a one-layer launch at the same machine fill, so
-// proportionally fewer fp32 partial slabs to write and reduce.
 hipError_t dg_conv_wgrad_multi(int kw, const long long* table, int nl, int dz_pad, int M,
                                int Mpad, int x_pad, int x_C, int B, int KP, int splits,
                                hipStream_t stream) {
@@ -1137,9 +1130,6 @@ hipError_t dg_wgrad_reduce(const float* slab, float* out, int splits, int M, int
   return hipGetLastError();
 }
 
-// Slab reduce + bias-gradient pass 2 of nl layers (any shapes) in one launch: table = nl
-// rows of `cols` int64 {slab, out (weight grad), bpart, gposb, gbias, splits, M, Mpad, KP,
-// taps, cin, cinp, bchunks[, out16, gposb16, gbias16]} (cols 13, or 16 with bf16 twins).
 hipError_t dg_wgrad_reduce_multi(const long long* table, int nl, int cols, hipStream_t stream) {
   if (nl <= 0 || nl > RD_MAXL || (cols != 13 && cols != 16)) return hipErrorInvalidValue;
   ReduceLayers Ls{};

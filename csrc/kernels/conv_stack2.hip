@@ -40,6 +40,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 #include "dg_features.h"
 #include "head_body.h"
@@ -652,25 +653,17 @@ extern "C" {
 
 void dg_conv_stack2_set_mode(int m) { g_stack2_mode = m; }
 
-// the staggered two-group schedule (overrides DG_STACK2_STAG): on 0 / 1, co-half-0 MFMA
-// priority 0..2, co-half-1 start delay (s_sleep 127 rounds)
 void dg_conv_stack2_set_sched(int stag, int prio, int delay) {
   g_stack2_stag = stag >= 0 && stag <= 2 ? stag : 0;
   g_stack2_prio = prio;
   g_stack2_delay = delay;
 }
 
-// table: nl rows of {A (fragment-ordered weights), pbias_frag, Y, mask} (int64 pointers)
-//   epi 1 (forward): pbias required, mask optional (written)
-//   epi 2 (dgrad)  : mask required (read; ReLU bits of the layer below), pbias unused
-// l1 (EPI_FWD only): row 0 is the network's first layer (5x5 over the [B][23][23][40] input
-// frame X0; its A = the [128][1024] weights in fragment order, k linear)
 hipError_t dg_conv_stack2(int epi, const long long* table, int nl, const void* X0, int l1, int B,
                           hipStream_t stream) {
   return stack2_launch(epi, table, nl, X0, l1, B, nullptr, stream);
 }
 
-// Forward stack + the 3x3 / 128-channel policy head fused after its last layer.
 hipError_t dg_conv_stack2_fwd_head(const long long* table, int nl, const void* X0, int l1, int B,
                                    const float* w, const float* bias, const float* posb,
                                    const int* labels, float* loss, int* pred, void* dZ,
@@ -681,8 +674,6 @@ hipError_t dg_conv_stack2_fwd_head(const long long* table, int nl, const void* X
   return stack2_launch(EPI_FWD, table, nl, X0, l1, B, &h, stream);
 }
 
-// The same with the feature expansion fused into the first layer's prologue (l1 only): the
-// packed batch's planes / player / rank in, the expanded frame X0 written out.
 hipError_t dg_conv_stack2_fwd_head_x(const long long* table, int nl, void* X0, int B,
                                      const void* planes, const void* player, const void* rank,
                                      const float* w, const float* bias, const float* posb,

@@ -48,6 +48,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 #include "head_body.h"
 
@@ -632,8 +633,6 @@ hipError_t launch_mode(int epi, const F8Args& a, int B, hipStream_t stream) {
   }
 }
 
-// table: nl rows of 8 int64 {A8, pbias, Y, mask, s_in, s_w, s_out, amax_out}
-
 hipError_t f8_launch(int C, int epi, const long long* table, int nl, const void* X0,
                      const float* s_x0, unsigned* amax_x0, int B, const dghead::HeadMArgs* head,
                      const long long* y8, const long long* sr_step, hipStream_t stream) {
@@ -686,8 +685,6 @@ extern "C" {
 
 void dg_conv_stack_f8_set_mode(int m) { g_f8_mode = m; }
 
-// the staggered schedule of C = 128 (overrides DG_STACK_F8_STAG): 0 off, 1 both stacks, 2
-// backward-data only; co-half-1 start delay (s_sleep 127 rounds)
 void dg_conv_stack_f8_set_debug(unsigned long long* dbg) { g_f8_dbg = dbg; }
 
 void dg_conv_stack_f8_set_sched(int stag, int delay) {
@@ -695,16 +692,12 @@ void dg_conv_stack_f8_set_sched(int stag, int delay) {
   g_f8_delay = delay;
 }
 
-// table: nl rows of {A8 (fragment-ordered e4m3 weights), pbias_frag, Y, mask, s_in, s_w,
-// s_out, amax_out} (int64); epi 1 forward, 2 backward-data; sr_step (backward-data): the
-// device step counter seeding stochastic rounding of the e5m2 gradients (null: nearest even)
 hipError_t dg_conv_stack_f8(int C, int epi, const long long* table, int nl, const void* X0,
                             const float* s_x0, unsigned* amax_x0, int B, const long long* y8,
                             const long long* sr_step, hipStream_t stream) {
   return f8_launch(C, epi, table, nl, X0, s_x0, amax_x0, B, nullptr, y8, sr_step, stream);
 }
 
-// C = 128: the head on the last layer's LDS image; 256: on its bf16 frame, read back
 hipError_t dg_conv_stack_f8_fwd_head(int C, const long long* table, int nl, const void* X0,
                                      const float* s_x0, unsigned* amax_x0, int B, const float* w,
                                      const float* bias, const float* posb, const int* labels,

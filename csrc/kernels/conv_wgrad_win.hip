@@ -23,6 +23,7 @@
 //
 // Reference semantics: SpatialConvolutionMM accGradParameters (experiments.lua:138, EXTERNAL
 // nn) — the gradient of the 3x3 hidden convolutions of getBasicModel (experiments.lua:135-149).
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -310,8 +311,7 @@ extern "C" {
 
 void dg_conv_wgrad_win_set_ablate(int mode) { g_win_ablate = mode; }
 
-// Splits per (layer, chunk pair) that fill num_cus CUs in one round (8 / NW workgroups per
-// CU).  At least 8 K-steps per split (the prologue loads a full window).
+// (8 / NW workgroups per CU)
 int dg_conv_wgrad_win_splits(int nl, int M, int Cx, int B, int num_cus) {
   const int pairs = nl * (M / (16 * WIN_NW)) * (Cx / 64);
   int s = pairs > 0 ? num_cus * (8 / WIN_NW) / pairs : 1;
@@ -320,7 +320,6 @@ int dg_conv_wgrad_win_splits(int nl, int M, int Cx, int B, int num_cus) {
   return s < 1 ? 1 : s;
 }
 
-// table = nl rows of {dZ frame (pad 1, M channels), X frame (pad 1, Cx channels), slab}.
 hipError_t dg_conv_wgrad_win(const long long* table, int nl, int M, int Mpad, int Cx, int B,
                              int KP, int splits, long long* sf, hipStream_t stream) {
   const int coch = 16 * WIN_NW;

@@ -48,6 +48,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -360,8 +361,6 @@ int dg_conv_wgrad_win8_splits(int nl, int M, int Cx, int B, int num_cus) {
   return best;
 }
 
-// table = nl rows of {dZ8 frame (pad 1, M channels, e5m2), X8 frame (pad 1, Cx channels,
-// e4m3), slab, s_dz, s_x} (int64)
 hipError_t dg_conv_wgrad_win8(const long long* table, int nl, int M, int Mpad, int Cx, int B,
                               int KP, int splits, long long* sf, hipStream_t stream) {
   const int cot = WIN8_COT;

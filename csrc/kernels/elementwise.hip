@@ -1,6 +1,7 @@
 // Memory-bound helper kernels: GPU feature expansion, per-channel / per-position bias
 // gradients, fused SGD / RMSProp updates, device-side LR decay and the bf16 weight
 // refresh that re-lays the fp32 OHWI master weights into the two MFMA operand layouts.
+#include "dg_api.h"
 #include "dg_common.h"
 #include "dg_features.h"
 
@@ -1021,7 +1022,6 @@ hipError_t dg_expand_features(const uint8_t* planes, const uint8_t* player, cons
   return hipGetLastError();
 }
 
-// part must hold nchunks*(361 + 19)*C floats, nchunks = ceil(B / 16)
 hipError_t dg_bias_grad_partial(const void* dZ, int B, int C, int pad, float* part,
                                 hipStream_t s) {
   if (C % 8 != 0 || C > 2048) return hipErrorInvalidValue;
@@ -1037,9 +1037,6 @@ hipError_t dg_bias_grad_partial(const void* dZ, int B, int C, int pad, float* pa
   return hipGetLastError();
 }
 
-// Pass 1 for nl same-shape layers in one launch: table = nl rows of {dZ frame, part, s8}
-// (s8: 0 = bf16 frame, else the e5m2 copy's scale pointer; pad must be 1 then);
-// chunks of BG_BT_MULTI boards (dg_bias_chunks_multi).
 hipError_t dg_bias_grad_partial_multi(const long long* table, int nl, int B, int C, int pad,
                                       long long* sf, hipStream_t s) {
   if (C % 8 != 0 || C > 2048 || nl <= 0 || nl > BG_MAXL) return hipErrorInvalidValue;
@@ -1062,7 +1059,6 @@ hipError_t dg_bias_grad_partial_multi(const long long* table, int nl, int B, int
 int dg_bias_chunks(int B) { return (B + BG_BT - 1) / BG_BT; }
 int dg_bias_chunks_multi(int B) { return (B + BG_BT_MULTI - 1) / BG_BT_MULTI; }
 
-// g16 (optional): read the bf16 twin gradient instead of g (data-parallel bf16 wire)
 hipError_t dg_sgd(float* p, const float* g, size_t n, const double* lr, float gscale,
                   const float* gate, const void* g16, hipStream_t s) {
   int blocks = (int)((n / 4 + 255) / 256);
@@ -1091,8 +1087,6 @@ hipError_t dg_rmsprop(float* p, const float* g, float* ms, size_t n, const doubl
   return hipGetLastError();
 }
 
-// loss (optional, rank-local) and grads (optional, flat, all-reduced; or its bf16 twin
-// grads16) -> gate in {0, 1}
 hipError_t dg_finite_gate(const float* loss, int n, const float* grads, size_t ng, float* gate,
                           int* bad_count, const void* grads16, hipStream_t s) {
   if (loss) {
@@ -1114,8 +1108,6 @@ hipError_t dg_finite_gate(const float* loss, int n, const float* grads, size_t n
   return hipGetLastError();
 }
 
-// gate = finite(loss) && finite(grads | grads16) in one launch (gate_all_kernel); ticket: one
-// zeroed word the launch leaves zeroed
 hipError_t dg_finite_gate1(const float* loss, int n, const float* grads, const void* grads16,
                            size_t ng, float* gate, int* bad_count, unsigned* ticket,
                            hipStream_t s) {
@@ -1143,11 +1135,7 @@ hipError_t dg_lr_decay(double* lr, double decay, long long* step, hipStream_t s)
   return hipGetLastError();
 }
 
-// layers: n entries of 20 int64 words
-//   {w, wf, wd, cout, cin, taps, cinp, kpf, kpd, pbias_frag, wf8, s_w, amax_w, bias, posb,
-//    pbias, wf_frag, wd_frag, wf8_frag, wd8_frag}  (pbias_frag / *_frag: stack-order tables,
-//    or 0)
-// lr (optional): fused per-step decay lr *= (1 - decay), step += 1 (see the kernel).
+// one 20-column refresh row (layout: dg_api.h dg_weight_refresh)
 static hipError_t parse_refresh_row(const long long* t, WRefreshLayer& L) {
   L.w = (const float*)t[0];
   L.wf = (bf16_t*)t[1];
@@ -1205,14 +1193,7 @@ hipError_t dg_weight_refresh(const long long* table, int n, double* lr, double d
   return hipGetLastError();
 }
 
-// The fused gradient pass 2 + optimizer + refresh (grad_update_kernel).  table: n rows of
-// GU_COLS int64 = the 20 weight_refresh columns, then {slab, bpart, splits, Mpad, KP,
-// bchunks, w_off, b_off, pos_off} (slab / bpart 0: the layer's gradient is read from G / G16).
-// plain_off / plain_n: a flat range updated from G only (the head).  tickets:
-// dg_grad_update_tickets() zeroed uint32 (left zeroed).  write_grads: with slabs, also store
-// the reduced gradient in G.  Tile blocks per row = dg_weight_refresh's block count (the fp8
-// |w| max slots), plus GU_NB bias blocks per 64-channel block of the widest layer.
-constexpr int GU_COLS = 29;
+constexpr int GU_COLS = 29;   // columns of a dg_grad_update row (layout: dg_api.h)
 int dg_grad_update_cols() { return GU_COLS; }
 int dg_grad_update_tickets() { return GU_TICKETS; }
 hipError_t dg_grad_update(const long long* table, int n, long long plain_off, long long plain_n,
@@ -1276,8 +1257,6 @@ hipError_t dg_grad_update(const long long* table, int n, long long plain_off, lo
   return hipGetLastError();
 }
 
-// nbytes of a bucket (multiple of 16), world = the ring size it stands in for, gbps = link
-// rate (GB/s; 0 = unpaced), blocks = channel workgroups
 hipError_t dg_comm_proxy(void* buf, long long nbytes, int world, double gbps, int blocks,
                          hipStream_t s) {
   if (!buf || nbytes < 16 || nbytes % 16 != 0 || world < 2 || blocks < 1 || blocks > 1024)

@@ -15,6 +15,7 @@
 // ds_read_b128), 4 pixels per wave.
 #include <stdlib.h>
 
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -408,11 +409,6 @@ static void allow_lds_once(K kernel, size_t bytes) {
     done = bytes;
   }
 }
-
-extern "C" hipError_t dg_head_mfma(int C, const void* X, int B, const float* w, const float* bias,
-                                   const float* posb, const int* labels, float* loss, int* pred,
-                                   float* logp_out, void* dZ, float* gw_part, float* dzb,
-                                   int head_relu, float grad_scale, hipStream_t stream);
 
 extern "C" hipError_t dg_head(int kw, const void* X, int x_pad, int C, int B, const float* w,
                               const float* bias, const float* posb, const int* labels,

@@ -21,6 +21,7 @@
 // Replaces head.hip's VALU dot/FMA loops for the 3x3 / 128-channel head (58 -> see
 // profiles/).  Reference: getBasicModel's last layer + Reshape + LogSoftMax
 // (experiments.lua:135-151), ClassNLLCriterion (:45), max/ne/sum accuracy (train.lua:29,36).
+#include "dg_api.h"
 #include "head_body.h"
 
 using namespace dg;
@@ -54,7 +55,6 @@ static hipError_t launch(int B, const HeadMArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// 3x3 head over a 128- or 256-channel pad-1 frame (the 12-layer configs); see dg_head.
 extern "C" hipError_t dg_head_mfma(int C, const void* X, int B, const float* w, const float* bias,
                                    const float* posb, const int* labels, float* loss, int* pred,
                                    float* logp_out, void* dZ, float* gw_part, float* dzb,

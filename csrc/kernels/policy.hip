@@ -8,6 +8,7 @@
 //
 // Plain C++ with wave shuffles: no atomics, every reduction in a fixed order, so the results
 // are bit-reproducible from run to run.
+#include "dg_api.h"
 #include "dg_common.h"
 
 using namespace dg;
@@ -184,8 +185,6 @@ policy_ensemble_kernel(const float* __restrict__ logp, const uint8_t* __restrict
 
 extern "C" {
 
-// The four destinations are the views of a packed batch buffer (data/batch.py) of capacity
-// B >= n S boards.
 hipError_t dg_symmetry_planes(const uint8_t* src_planes, const uint8_t* src_player,
                               const uint8_t* src_rank, const int* src_labels, int n, int S,
                               uint8_t* planes, uint8_t* player, uint8_t* rank, int* labels,
@@ -202,8 +201,6 @@ hipError_t dg_symmetry_planes(const uint8_t* src_planes, const uint8_t* src_play
   return hipGetLastError();
 }
 
-// logp [n S][361]; stones: plane 0 of the UNtransformed positions, board stride
-// stones_stride bytes; extra_illegal [n][361] (nonzero = illegal) and labels [n] optional.
 hipError_t dg_policy_ensemble(const float* logp, const uint8_t* stones, int stones_stride,
                               const uint8_t* extra_illegal, const int* labels, int n, int S,
                               int K, int mask, float* prob, int* topk_idx, float* topk_p,

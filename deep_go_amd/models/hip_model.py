@@ -53,7 +53,7 @@ FP8_G_HEADROOM = 4.0
 FP8_GHIST = 16        # gradient amax history length (conv_fp8.hip FP8_GHIST)
 REFRESH_PARTS = 512   # weight_refresh workgroups per layer (elementwise.hip)
 
-# Columns of the int64 launch tables that are edited after the table is built.
+# Columns of the int64 launch tables (layouts: csrc/kernels/dg_api.h) edited after the build.
 # Refresh row (_build_refresh_table; csrc/kernels/elementwise.hip parse_refresh_row): the
 # optional operand-copy outputs (a null pointer: that copy is not written)
 RT_WEIGHT_COPIES = {1: "wf", 2: "wd", 10: "wf8", 16: "wf_frag", 17: "wd_frag",
