@@ -151,10 +151,12 @@ def conv_board(x: torch.Tensor, w: torch.Tensor, bias=None, posb=None, epi: str 
 
 
 def conv_board_fp8(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, posb: torch.Tensor,
-                   bm: int | None = None):
+                   bm: int | None = None, s_x: float | None = None, s_w: float | None = None,
+                   s_y: float = 1.0 / 64):
     """FP8 forward (conv_fp8.hip): x [B,Cin,19,19] (Cin % 128 == 0), OHWI w, fp32 bias/posb.
-    Quantizes x / w with per-tensor scales (amax / 448) through the same device kernels the
-    model uses; returns (y bf16-frame interior as fp32 NCHW, y8 dequantized, s_y, amax_y)."""
+    Quantizes x / w with per-tensor scales (amax / 448, or the given s_x / s_w) through the
+    same device kernels the model uses; returns (y bf16-frame interior as fp32 NCHW, y8
+    dequantized, s_y, amax_y)."""
     h = hip()
     dev = w.device
     B = x.shape[0]
@@ -165,15 +167,18 @@ def conv_board_fp8(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, posb: t
     s = stream_handle()
     wflat = w.float().contiguous().to(dev)
     scales = (wflat.abs().max() / 448.0).clamp_min(1e-12).reshape(1)  # s_w
+    if s_w is not None:
+        scales = torch.full((1,), float(s_w), device=dev)
     A8 = torch.zeros((Mpad, KP), dtype=torch.uint8, device=dev)
     h.weight_fp8(wflat.data_ptr(), A8.data_ptr(), cout, cin, k * k, cin, KP, scales.data_ptr(), s)
     xf = LY.to_frame(x.to(dev), pad, cin)
-    s_x = (xf.float().abs().max() / 448.0).clamp_min(1e-12).reshape(1)
+    s_x = (torch.full((1,), float(s_x), device=dev) if s_x is not None
+           else (xf.float().abs().max() / 448.0).clamp_min(1e-12).reshape(1))
     x8 = torch.zeros(xf.numel(), dtype=torch.uint8, device=dev)
     h.frame_to_fp8(xf.data_ptr(), x8.data_ptr(), xf.numel(), s_x.data_ptr(), 0, s)
     y = LY.alloc_frame(B, cout, 1, dev)
     y8 = torch.zeros(y.numel(), dtype=torch.uint8, device=dev)
-    s_y = torch.full((1,), 1.0 / 64, device=dev)
+    s_y = torch.full((1,), float(s_y), device=dev)
     amax_y = torch.zeros(1, dtype=torch.int32, device=dev)
     h.conv_board_fp8(k, bm, A8.data_ptr(), KP, cout, Mpad, x8.data_ptr(), pad, cin, B,
                      y.data_ptr(), y8.data_ptr(), 1, bias.float().contiguous().to(dev).data_ptr(),
@@ -205,10 +210,12 @@ def conv_dgrad(dz: torch.Tensor, w: torch.Tensor, aux: torch.Tensor, tiles=None)
 
 
 def conv_wgrad(dz: torch.Tensor, x: torch.Tensor, k: int, splits: int | None = None,
-               cinp: int | None = None, with_bias: bool = False, algo: str = "auto"):
+               cinp: int | None = None, with_bias: bool = False, algo: str = "auto",
+               sf: torch.Tensor | None = None):
     """dW[co][kh][kw][ci] = sum_{b,p} dz[b,co,p] * x[b,ci,p+off] (fp32 OHWI).
 
-    with_bias=True also returns the fused bias grads (gposb [361][co], gbias [co])."""
+    with_bias=True also returns the fused bias grads (gposb [361][co], gbias [co]).
+    sf: the int64 {step, bad-step tag} pair handed to the launches that take one."""
     h = hip()
     dev = dz.device
     B, cout = dz.shape[:2]
@@ -229,9 +236,9 @@ def conv_wgrad(dz: torch.Tensor, x: torch.Tensor, k: int, splits: int | None = N
         out = torch.empty((cout, k, k, cin), dtype=torch.float32, device=dev)
         table = torch.tensor([[dzf.data_ptr(), xf.data_ptr(), slab.data_ptr()]], dtype=torch.int64)
         s = stream_handle()
-        h.conv_wgrad_win(table.data_ptr(), 1, cout, Mpad, cinp, B, KPw, splits, 0, s)
+        h.conv_wgrad_win(table.data_ptr(), 1, cout, Mpad, cinp, B, KPw, splits, _ptr(sf), s)
         h.wgrad_reduce(slab.data_ptr(), out.data_ptr(), splits, cout, Mpad, KPw, 9, cin, cinp,
-                       0, 0, 0, 0, 0, s)
+                       0, 0, 0, 0, _ptr(sf), s)
         torch.cuda.synchronize(dev)
         return out
     splits = splits or LY.pick_wgrad_splits(npix, KPw, Mpad,
@@ -250,7 +257,7 @@ def conv_wgrad(dz: torch.Tensor, x: torch.Tensor, k: int, splits: int | None = N
     h.conv_wgrad(k, dzf.data_ptr(), max(1, pad), cout, Mpad, xf.data_ptr(), pad, cinp, B,
                  KPw, splits, slab.data_ptr(), s)
     h.wgrad_reduce(slab.data_ptr(), out.data_ptr(), splits, cout, Mpad, KPw, k * k, cin, cinp,
-                   bpart.data_ptr(), nch, gp.data_ptr(), gb.data_ptr(), 0, s)
+                   bpart.data_ptr(), nch, gp.data_ptr(), gb.data_ptr(), _ptr(sf), s)
     if with_bias:
         return out, gp, gb
     return out
