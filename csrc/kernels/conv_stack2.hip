@@ -67,8 +67,10 @@ constexpr int SCRATCH = 12 * 1024;        // head_body scratch (fused head)
 constexpr int STEP_BYTES = 2 * 2 * MF * 64 * 16;   // one K-step of one layer: 16 KB
 constexpr int WM_BYTES = STEP_BYTES / 2;           // one co-half: 8 KB
 constexpr int CO_STEPS = (NPTS * 8 + NT - 1) / NT;  // copy-out steps per 64-channel image (6)
+constexpr int CO_TAB = CO_STEPS * (NT / 8);         // copy-out table entries (384 x 4 B)
 
 static_assert(dghead::scratch_bytes(C) <= SCRATCH, "head scratch");
+static_assert(CO_TAB <= NT && CO_TAB * 4 <= SCRATCH - 16, "copy-out table in the head scratch");
 
 struct StackLayer {
   const char* A;        // fragment-ordered weights (18 x 16 KB; dgrad: flipped, transposed)
@@ -152,6 +154,14 @@ DG_DEV uint32_t pair_mask(uint32_t nib) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 0, 1);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 1, 1);
   return __builtin_amdgcn_perm(hi, lo, 0x07060100u);
+}
+
+// packed 16-bit halves in [0, 0x7fff] (post-ReLU bf16) -> 1 where the half is nonzero: one
+// v_pk_min_i16 with 1 (signed on purpose: the compiler rewrites the unsigned min as compares
+// and selects)
+DG_DEV uint32_t nz16x2(uint32_t u) {
+  return __builtin_bit_cast(
+      uint32_t, __builtin_elementwise_min(__builtin_bit_cast(s16x2, u), s16x2{1, 1}));
 }
 
 // (the staggered schedule's LDS counters: grp_signal / grp_wait, dg_common.h)
@@ -300,30 +310,44 @@ __global__ void __launch_bounds__(NT) conv_stack2_kernel(StackArgs a) {
   // piece of a step is read from LDS after the step's first k-half and stored at its end.
   // Step s: half hf = s / 9, j = s % 9; thread tid handles channel piece q = tid & 7 of
   // image hf at pixel p = tid / 8 + 64 j (128 contiguous bytes per pixel and image).
-  auto co_read = [&](int s_) -> uint4 {
-    const int hf = s_ >= T, j = s_ - hf * T;
-    const int p = min((tid >> 3) + 64 * j, NPTS - 1);
+  //
+  // Everything that depends on the pixel alone comes from a table built once per kernel in
+  // the head scratch (unused until the head; clear of the STAG counters in its last 16 B):
+  // entry e < 384 describes pixel p = min(e, 360) (entries past the board repeat pixel 360:
+  // every wave issues the stores) with frame row f = (h + 1) * 21 + (w + 1):
+  //   bits 0..15  f * 128 | fsig(f) << 4   (the row's LDS offset; XOR with q * 16 = the piece;
+  //               bits 0..3 are zero: masking them keeps the 16-B alignment visible)
+  //   bits 16..24 p                         (the ReLU-bit row)
+  // One ds_read_b32 per copy-out step replaces two divisions per thread and step.
+  if (tid < CO_TAB) {
+    const int p = min(tid, NPTS - 1);
     const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
     const int f = (h + 1) * F + (w + 1);
-    return *(const uint4*)(sH + hf * H_BYTES + f * 128 + (((tid & 7) ^ fsig(f)) * 16));
+    ((uint32_t*)smem)[tid] = (uint32_t)(f * 128) | ((uint32_t)fsig(f) << 4) | ((uint32_t)p << 16);
+  }
+  auto co_read = [&](int s_, uint32_t& e) -> uint4 {
+    const int hf = s_ >= T, j = s_ - hf * T;
+    e = ((const uint32_t*)smem)[(tid >> 3) + 64 * j];
+    return __builtin_bit_cast(uint4, lds_read_b128((const LDS_AS char*)sH + hf * H_BYTES +
+                                                   ((e & 0xFFF0u) ^ ((tid & 7) << 4))));
   };
-  auto co_store = [&](int s_, const uint4& v, const StackLayer& Lo) {
-    // lanes past the board re-store pixel 360 (same value): every wave issues the stores
-    const int hf = s_ >= T, j = s_ - hf * T;
-    const int p = min((tid >> 3) + 64 * j, NPTS - 1);
-    const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
-    const int f = (h + 1) * F + (w + 1);
-    const int co_q = hf * 8 + (tid & 7);
-    *(uint4*)(Lo.Y + ((size_t)(b * FF + f) * C) * 2 + co_q * 16) = v;
+  auto co_store = [&](int s_, const uint4& v, uint32_t e, const StackLayer& Lo) {
+    const int hf = s_ >= T;
+    // (wave-uniform base + 32-bit lane offset: f * 256 + the piece's 16 B).  Non-temporal:
+    // the frame is next read by the weight-gradient kernels, long after it has left L2, and
+    // kept out of L2 it does not displace the weights every board re-reads (12x128 step
+    // +1.6 % on top of the table, profiles/r7_stack_kloop.txt)
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(
+        u32x4{v.x, v.y, v.z, v.w},
+        (u32x4*)(Lo.Y + (size_t)b * (FF * C * 2) + hf * 128 + (((e & 0xFF80u) << 1) + ((tid & 7) << 4))));
     if (EPI == EPI_FWD && Lo.mask) {
-      // bit per nonzero bf16 half (post-ReLU: every half is in [0, 0x7fff]): h + 0x7fff has
-      // bit 15 set iff h != 0, with no carry out of the half; gather bits 15 / 31 of the
-      // four words to channel order (bit 2k: word k low half, 2k + 1: its high half)
-      const uint32_t m = (((v.x + 0x7fff7fffu) >> 15) & 0x10001u) |
-                         (((v.y + 0x7fff7fffu) >> 13) & 0x40004u) |
-                         (((v.z + 0x7fff7fffu) >> 11) & 0x100010u) |
-                         (((v.w + 0x7fff7fffu) >> 9) & 0x400040u);
-      Lo.mask[((size_t)b * NPTS + p) * 16 + co_q] = (uint8_t)(m | (m >> 15));
+      // bit per nonzero bf16 half: min(h, 1) per packed half (nz16x2) is bit 0 / 16 of
+      // its word; gather the four words to channel order (bit 2k: word k low half, 2k + 1:
+      // its high half)
+      const uint32_t m = nz16x2(v.x) | (nz16x2(v.y) << 2) | (nz16x2(v.z) << 4) | (nz16x2(v.w) << 6);
+      Lo.mask[(size_t)b * (NPTS * 16) + hf * 8 + (((e >> 16) << 4) + (tid & 7))] =
+          (uint8_t)(m | (m >> 15));
     }
   };
 
@@ -345,6 +369,7 @@ __global__ void __launch_bounds__(NT) conv_stack2_kernel(StackArgs a) {
       for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     uint4 co_v;
+    uint32_t co_e;
 
     // One K-step.  A k-half's fragments (the next step's) are re-loaded right after that
     // k-half's MFMAs are issued: one register set, half a step of prefetch distance.  Plain
@@ -359,20 +384,26 @@ __global__ void __launch_bounds__(NT) conv_stack2_kernel(StackArgs a) {
       mma(Ak[0], bfr, acc);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (!(MODE & 2)) load_A(An, 0, Ak[0]);
-      if (co) co_v = co_read(s);
+      if (co) co_v = co_read(s, co_e);
       if constexpr (!(MODE & 8)) read_B(s, 1, bfr);
       __builtin_amdgcn_sched_barrier(0);
       mma(Ak[1], bfr, acc);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (!(MODE & 2)) load_A(An, 1, Ak[1]);
-      if (co) co_store(s, co_v, Lprev);
+      if (co) co_store(s, co_v, co_e, Lprev);
       __builtin_amdgcn_sched_barrier(0);
     };
-    // Rolled loops with a per-step copy-out branch.  The compiler's wait at their head is
-    // then vmcnt(0) (the k-half-1 loads of the step before and its copy-out store drain
-    // there); measured faster than every variant with exact waits: two branch-free loops
-    // (copy-out steps / the rest: fwd 229 -> 234 us, dgrad 216 -> 224 us) and unrolled by 2
-    // or 3 (267 / 279 us; profiles/r2_kbench_stack2.json).
+    // Two rolled, branch-free loops per image: its 6 copy-out steps, then the rest (unrolled
+    // by 2 or 3: 267 / 279 us, profiles/r2_kbench_stack2.json).  The compiler's waits
+    // (tools/kloop_report.py): the forward waits for each A fragment exactly (vmcnt 7..4 per
+    // k-half).  The backward-data kernels begin every image-0 K-step (barrier schedule: every
+    // K-step) with a full vmcnt(0), and the cause is outside the loop: the scheduler emits
+    // the prologue's eight fragment loads in reverse, fragment 0 of k-half 0 last, so on the
+    // way in from the prologue the first MFMA needs vmcnt(0), and a wait at a loop head has
+    // to hold for every path into it.  Issuing the prologue's loads in the loop's order (a
+    // sched_barrier between them) makes every wait exact — and measured no faster (barrier
+    // schedule equal, staggered schedule +0.5 %: profiles/r7_stack_kloop.txt), so the
+    // prologue stays as it is.
     //
     // Two-group schedule of the backward-data chain (TWO_GROUP; the waves of co-half wm write
     // image wm in the epilogue):
@@ -544,8 +575,12 @@ __global__ void __launch_bounds__(NT) conv_stack2_kernel(StackArgs a) {
   // the head-less launch; the head's backward gates with the image itself, not the bitmask
   if (EPI != EPI_FWD || !a.fuse_head) {
     const StackLayer Ll = a.L[a.nl - 1];
-    for (int s_ = 0; s_ < CO_STEPS; ++s_) co_store(s_, co_read(s_), Ll);
-    for (int s_ = T; s_ < T + CO_STEPS; ++s_) co_store(s_, co_read(s_), Ll);
+    for (int hf = 0; hf < 2; ++hf)
+      for (int s_ = hf * T; s_ < hf * T + CO_STEPS; ++s_) {
+        uint32_t e;
+        const uint4 v = co_read(s_, e);
+        co_store(s_, v, e, Ll);
+      }
   }
   // the policy head on the board image that is already in LDS (no re-staging, no launch)
   if constexpr (EPI == EPI_FWD) {

@@ -29,6 +29,9 @@ CXX = os.environ.get("CXX", "g++")
 EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
 HIP_SOURCES = ["conv_mfma.hip", "conv_board.hip", "conv_stack2.hip", "conv_layer2.hip", "conv_stack_f8.hip", "conv_wgrad_win.hip", "conv_wgrad_win8.hip", "conv_l1.hip", "conv_fp8.hip", "head.hip", "head_mfma.hip", "elementwise.hip", "policy.hip", "bindings.cpp"]
+# the kernels' compile flags (tools/kloop_report.py compiles with the same ones)
+HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
+             "-Wno-unused-result"]
 CPU_SOURCES = ["go_engine.cpp", "sgf.cpp", "t7.cpp", "features.cpp", "loader.cpp",
                "bindings.cpp"]
 
@@ -65,8 +68,7 @@ def build_hip(force: bool = False, jobs: int = 8) -> Path:
         obj = BUILD / ("hip_" + s + ".o")
         objs.append(obj)
         if force or _newer(src, obj, headers):
-            cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
-                   "-munsafe-fp-atomics", "-Wno-unused-result", "-c", str(src), "-o", str(obj)]
+            cmd = [HIPCC, *HIP_FLAGS, "-c", str(src), "-o", str(obj)]
             if s.endswith(".cpp"):
                 cmd = [HIPCC, "-O2", "-std=c++17", "-fPIC", *(_pybind_includes()), "-c",
                        str(src), "-o", str(obj)]

@@ -98,6 +98,18 @@ def stack_pbias_frag(bias: torch.Tensor, posb: torch.Tensor) -> torch.Tensor:
     return a.permute(2, 0, 3, 4, 5, 1, 6).reshape(-1).contiguous()
 
 
+def stack_copyout_table() -> torch.Tensor:
+    """conv_stack2's per-pixel copy-out table as the kernel builds it in LDS (int64 [384]): entry
+    e describes pixel p = min(e, 360) = 19 h + w with frame row f = 21 (h + 1) + (w + 1):
+    bits 0..15 f*128 | sig << 4 with the row's XOR-swizzle signature sig = ((f % 21) +
+    3 (f // 21)) & 7 (the row's byte offset in a 64-channel LDS image; XOR with 16 q is channel
+    piece q), bits 16..24 p (the row of the ReLU bits).  (tests/test_stack_copyout_cpu.py)"""
+    p = torch.arange(6 * 64).clamp(max=360)
+    f = (p // BOARD + 1) * 21 + (p % BOARD + 1)
+    sig = ((f % 21) + 3 * (f // 21)) & 7
+    return (f * 128) | (sig << 4) | (p << 16)
+
+
 def stack_frag_f8(w8: torch.Tensor) -> torch.Tensor:
     """conv_stack_f8 A-operand order of e4m3 forward weights ``w8`` [C co][9 taps][C ci]
     (uint8 bytes, C = 128 | 256).
