@@ -297,4 +297,16 @@ hipError_t dg_policy_ensemble(const float* logp, const uint8_t* stones, int ston
                               int K, int mask, float* prob, int* topk_idx, float* topk_p,
                               int* label_rank, hipStream_t s);
 
+// ---------------------------------------------------------------- augment.hip (module _dgaug)
+// Every board i < B of a packed batch (planes [B][9][361], labels [B]) moved IN PLACE by the
+// board symmetry s_i: sym[i] & 7 when sym (optional, uint8 [B]) is given, else
+// dg_augment_symmetry(seed, seq, board0 + i).  A label in 0..360 becomes T_s(label), any other
+// value stays; a board with s = 0 is not written.  sym_out (optional, uint8 [B]): the ids used.
+hipError_t dg_augment_batch(uint8_t* planes, int* labels, int B, const uint8_t* sym,
+                            unsigned long long seed, unsigned long long seq,
+                            unsigned long long board0, uint8_t* sym_out, hipStream_t stream);
+// The hash behind it, on the host (data/symmetry.py augment_symmetries is the definition).
+int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
+                        unsigned long long board);
+
 }  // extern "C"

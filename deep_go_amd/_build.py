@@ -1,10 +1,12 @@
 """In-tree native build: hipcc for the gfx950 kernels, g++ for the CPU engine.
 
-Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11) and
+Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
+``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|cpu] [--sanitize thread|address]``
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|cpu|comm]
+[--sanitize thread|address]``
 """
 from __future__ import annotations
 
@@ -81,6 +83,29 @@ def build_hip(force: bool = False, jobs: int = 8) -> Path:
     return target
 
 
+def build_aug(force: bool = False) -> Path:
+    """_dgaug: the training-time symmetry augmentation (augment.hip + its two bindings), apart
+    from _dghip so that module's recorded interface stays as it is."""
+    BUILD.mkdir(exist_ok=True)
+    OUT.mkdir(exist_ok=True)
+    target = OUT / f"_dgaug{EXT}"
+    headers = list(KDIR.glob("*.h"))
+    kern, kobj = KDIR / "augment.hip", BUILD / "aug_augment.hip.o"
+    bind, bobj = KDIR / "aug_bindings.cpp", BUILD / "aug_bindings.cpp.o"
+    built = False
+    if force or _newer(kern, kobj, headers):
+        _run([HIPCC, *HIP_FLAGS, "-c", str(kern), "-o", str(kobj)])
+        built = True
+    if force or _newer(bind, bobj, headers):
+        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", *(_pybind_includes()), "-c", str(bind), "-o",
+              str(bobj)])
+        built = True
+    if force or built or not target.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "--hip-link", "-o",
+              str(target), str(kobj), str(bobj)])
+    return target
+
+
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
     BUILD.mkdir(exist_ok=True)
     OUT.mkdir(exist_ok=True)
@@ -133,13 +158,14 @@ def build_comm(force: bool = False) -> Path:
 def build_all(force: bool = False) -> None:
     build_cpu(force)
     build_hip(force)
+    build_aug(force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -147,6 +173,8 @@ def main(argv=None):
         print(build_cpu(a.force, a.j, a.sanitize))
     if a.only in (None, "hip") and not a.sanitize:
         print(build_hip(a.force, a.j))
+    if a.only in (None, "aug") and not a.sanitize:
+        print(build_aug(a.force))
     if a.only in (None, "comm") and not a.sanitize:
         print(build_comm(a.force))
 

@@ -82,6 +82,10 @@ class ExperimentConfig:
     # optional 38th input plane: the simple-ko point (needs data made with makedata --ko;
     # off = the reference's 37-plane layout)
     ko_plane: bool = False
+    # training-time data augmentation: none | d4 (every board of every training batch moved by
+    # one of the 8 board symmetries, drawn by data/symmetry.py augment_symmetries from (seed,
+    # loader sequence number, board index); validation, eval and predict are not augmented)
+    augment: str = "none"
     id: Optional[str] = None
 
     # ---- derived layer schedule ----
@@ -172,7 +176,7 @@ def _coerce(name: str, value: Any, current: Any) -> Any:
 
 _CHOICES = {"nan_policy": ("guard", "skip", "raise"), "comm": ("auto", "native", "torch"),
             "optimizer": ("sgd", "rmsprop"), "grad_dtype": ("fp32", "bf16"),
-            "sampling": ("game", "position")}
+            "sampling": ("game", "position"), "augment": ("none", "d4")}
 
 
 def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:

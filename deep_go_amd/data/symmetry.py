@@ -10,6 +10,10 @@ A point is ``p = 19*x + y`` (the label convention of ``data/features.py``).  For
 ``s = 0`` is the identity.  The GPU forms are ``symmetry_planes`` and ``policy_ensemble``
 (csrc/kernels/policy.hip); this module is what the CPU path of ``deep_go_amd.predict`` runs
 and what the tests compare the kernels with.
+
+Training-time augmentation (``augment=d4``): ``augment_symmetries`` defines which symmetry
+every board of every training batch gets, ``augment_batch`` is the numpy oracle of the
+transform; csrc/kernels/augment.hip is the GPU form of both.
 """
 from __future__ import annotations
 
@@ -58,6 +62,64 @@ def transform_label(label, s: int):
     lab = np.asarray(label, dtype=np.int64)
     out = np.where(lab >= 0, SYM_PERM[s].astype(np.int64)[np.clip(lab, 0, NUM_POINTS - 1)], -1)
     return int(out) if out.ndim == 0 else out.astype(np.int32)
+
+
+# the inverse element: T_{SYM_INVERSE[s]} undoes T_s
+SYM_INVERSE = np.array([next(t for t in range(NUM_SYMMETRIES)
+                             if (SYM_PERM[t][SYM_PERM[s]] == np.arange(NUM_POINTS)).all())
+                        for s in range(NUM_SYMMETRIES)], np.uint8)
+SYM_INVERSE.setflags(write=False)
+
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x: np.ndarray) -> np.ndarray:
+    """The "lowbias32" finaliser on uint32 arrays (arithmetic mod 2^32)."""
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def augment_symmetries(seed: int, seq: int, board0: int, n: int) -> np.ndarray:
+    """uint8 [n]: the symmetry id of boards ``board0 .. board0 + n - 1`` of the training batch
+    with loader sequence number ``seq``.  A pure 32-bit integer hash of all 64 bits of ``seed``
+    and ``seq`` and the low 32 bits of the board index, with no generator state: exact under
+    resume, and what the kernel repeats bit for bit (augment.hip hash_symmetry).  With ``mix32``
+    the lowbias32 finaliser::
+
+        a = mix32((seed_lo ^ 0x9e3779b9) + seed_hi)
+        b = mix32(mix32(a + seq_lo) ^ seq_hi)
+        s = mix32(b + board_lo) >> 29
+    """
+    seed, seq = int(seed) & (2 ** 64 - 1), int(seq) & (2 ** 64 - 1)
+    u = lambda v: np.array([v & _M32], np.uint32)   # noqa: E731
+    with np.errstate(over="ignore"):
+        a = _mix32((u(seed) ^ np.uint32(0x9e3779b9)) + u(seed >> 32))
+        b = _mix32(_mix32(a + u(seq)) ^ u(seq >> 32))
+        board = ((int(board0) + np.arange(n, dtype=np.uint64)) & np.uint64(_M32)).astype(np.uint32)
+        return (_mix32(b + board) >> np.uint32(29)).astype(np.uint8)
+
+
+def augment_batch(planes: np.ndarray, labels: np.ndarray, sym) -> Tuple[np.ndarray, np.ndarray]:
+    """The numpy oracle of the training-time augmentation: new ``(planes, labels)`` with board
+    ``i`` moved by ``T_sym[i]`` (every stored plane, so a ko mark in the liberty plane moves
+    with its point) and a label in ``0..360`` replaced by ``T_s(label)``; any other label value
+    stays as it is.  ``planes [n, 9, 19, 19]`` or ``[n, 9, 361]``; player and rank are not
+    involved."""
+    planes, labels = np.asarray(planes), np.asarray(labels)
+    sym = np.asarray(sym).astype(np.int64) & 7
+    if not (len(planes) == len(labels) == len(sym)):
+        raise ValueError(f"{len(planes)} boards, {len(labels)} labels, {len(sym)} symmetries")
+    out_p, out_l = planes.copy(), labels.copy()
+    for i, s in enumerate(sym):
+        if s == 0:
+            continue
+        out_p[i] = transform_planes(planes[i], int(s))
+        if 0 <= labels[i] < NUM_POINTS:
+            out_l[i] = transform_label(int(labels[i]), int(s))
+    return out_p, out_l
 
 
 def ensemble_policy(logp: np.ndarray, legal: np.ndarray, K: int,

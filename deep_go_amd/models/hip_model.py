@@ -410,6 +410,9 @@ class HipGoNet:
         self.cur_in = 0
         self.load_stream = None
         self._in_ops = None
+        # training-time symmetry augmentation (set_augment): off until armed
+        self._aug = None
+        self.aug_sym: Optional[torch.Tensor] = None
         self.loss = torch.zeros(B, dtype=torch.float32, device=dev)
         self.pred = torch.zeros(B, dtype=torch.int32, device=dev)
         # evaluation writes its own outputs so it never clobbers the training step's loss
@@ -1167,15 +1170,43 @@ class HipGoNet:
         self.inbuf = self._inbufs[k]
         self.planes, self.player, self.rank, self.labels = self._in_views[k]
 
-    def _load(self, fill, device_src: bool):
+    def set_augment(self, seed: int, board0: int = 0):
+        """Arm the training-time symmetry augmentation: a ``set_batch*`` call given the batch's
+        loader sequence number (``aug_seq``) then moves board ``i`` of that batch, in place in
+        the input buffer, by symmetry ``augment_symmetries(seed, aug_seq, board0 + i)``
+        (data/symmetry.py; csrc/kernels/augment.hip).  ``board0``: this rank's first board in
+        the global batch.  ``aug_sym`` (uint8 [B], device) holds the ids of the last augmented
+        batch.  The kernel's module is imported here, not before."""
+        from ..ops.native import aug
+        self._aug = aug()
+        m64 = 2 ** 64 - 1
+        self._aug_seed, self._aug_board0 = int(seed) & m64, int(board0) & m64
+        if self.aug_sym is None:
+            self.aug_sym = torch.zeros(self.B, dtype=torch.uint8, device=self.device)
+
+    def _augment(self, views, aug_seq: int):
+        """The augmentation launch on the current stream, over the buffer whose views these
+        are: right behind the copy that filled it."""
+        if self._aug is None:
+            raise RuntimeError("aug_seq given but augmentation is not armed (set_augment)")
+        self._aug.augment_batch(views[0].data_ptr(), views[3].data_ptr(), self.B, 0,
+                                self._aug_seed, int(aug_seq) & (2 ** 64 - 1), self._aug_board0,
+                                self.aug_sym.data_ptr(), stream_handle())
+
+    def _load(self, fill, device_src: bool, aug_seq: Optional[int] = None):
         """Run ``fill(buffer, views)`` for the next batch: in place without prefetch; with it,
         into the other buffer on the load stream (after the step that last read it), and the
         compute stream waits for the copy before the next step's launches.  A device source
         may still be being written by work issued on the compute stream, so then the load
         stream waits for all of it (the overlap is for host sources: the loader's pinned
-        slots, copied by the SDMA engines)."""
+        slots, copied by the SDMA engines).  With ``aug_seq`` (the batch's loader sequence
+        number; set_augment) the augmentation kernel follows the copy on the same stream, before
+        anything else can see the batch."""
         if self.load_stream is None:
-            fill(self.inbuf, (self.planes, self.player, self.rank, self.labels))
+            views = (self.planes, self.player, self.rank, self.labels)
+            fill(self.inbuf, views)
+            if aug_seq is not None:
+                self._augment(views, aug_seq)
         else:
             main = torch.cuda.current_stream(self.device)
             self._rel_ev[self.cur_in].record(main)       # all issued reads of the current one
@@ -1183,6 +1214,8 @@ class HipGoNet:
             self.load_stream.wait_event(self._rel_ev[1 - t if device_src else t])
             with torch.cuda.stream(self.load_stream):
                 fill(self._inbufs[t], self._in_views[t])
+                if aug_seq is not None:
+                    self._augment(self._in_views[t], aug_seq)
                 ready = torch.cuda.Event()
                 ready.record(self.load_stream)
             if self.sc:
@@ -1195,8 +1228,10 @@ class HipGoNet:
             self.calibrate_fp8()
 
     def set_batch(self, planes: torch.Tensor, player: torch.Tensor, rank: torch.Tensor,
-                  labels: torch.Tensor, non_blocking: bool = True):
-        """Copy one batch into the static input buffers (device or pinned host tensors)."""
+                  labels: torch.Tensor, non_blocking: bool = True,
+                  aug_seq: Optional[int] = None):
+        """Copy one batch into the static input buffers (device or pinned host tensors).
+        ``aug_seq``: see ``_load`` (None: the batch as given)."""
         def fill(_, v):
             v[0].copy_(planes.reshape(self.B, 9, NUM_POINTS), non_blocking=non_blocking)
             v[1].copy_(player, non_blocking=non_blocking)
@@ -1206,20 +1241,21 @@ class HipGoNet:
                 for x in (planes, player, rank, labels):
                     if x.is_cuda:
                         x.record_stream(self.load_stream)
-        self._load(fill, any(x.is_cuda for x in (planes, player, rank, labels)))
+        self._load(fill, any(x.is_cuda for x in (planes, player, rank, labels)), aug_seq)
 
-    def set_batch_packed(self, packed: torch.Tensor, non_blocking: bool = True):
+    def set_batch_packed(self, packed: torch.Tensor, non_blocking: bool = True,
+                         aug_seq: Optional[int] = None):
         """One copy of a ``pack_batch`` buffer (device or pinned host) into the inputs."""
         def fill(buf, _):
             buf.copy_(packed, non_blocking=non_blocking)
             if packed.is_cuda and self.load_stream is not None:
                 packed.record_stream(self.load_stream)
-        self._load(fill, packed.is_cuda)
+        self._load(fill, packed.is_cuda, aug_seq)
 
-    def set_batch_packed_from(self, loader):
+    def set_batch_packed_from(self, loader, aug_seq: Optional[int] = None):
         """Next batch of a BatchLoader with pinned packed slots: one async copy (the loader
         releases the slot on an event recorded on the stream that copied it)."""
-        self._load(lambda buf, _: loader.next_packed_to(buf), False)
+        self._load(lambda buf, _: loader.next_packed_to(buf), False, aug_seq)
 
     def forward(self):
         s = stream_handle()

@@ -388,6 +388,27 @@ def symmetry_planes(planes: torch.Tensor, player: torch.Tensor, rank: torch.Tens
     return out, v
 
 
+def augment_batch(buf: torch.Tensor, B: int, sym: torch.Tensor | None = None, seed: int = 0,
+                  seq: int = 0, board0: int = 0, want_ids: bool = True):
+    """Move the B boards of a packed device batch buffer (data/batch.py layout) in place by
+    board symmetries (augment.hip): ``sym`` uint8 [B] gives them (``& 7``), else they are
+    ``augment_symmetries(seed, seq, board0, B)`` (data/symmetry.py, the definition;
+    ``augment_batch`` there is the oracle).  Returns the uint8 [B] ids used (None without
+    ``want_ids``)."""
+    from ..data.batch import packed_batch_bytes, unpack_views
+    from .native import aug
+    assert buf.is_cuda and buf.dtype == torch.uint8 and buf.numel() == packed_batch_bytes(B)
+    v = unpack_views(buf, B)
+    if sym is not None:
+        sym = sym.to(buf.device, torch.uint8).contiguous()
+        assert sym.numel() == B
+    ids = torch.zeros(B, dtype=torch.uint8, device=buf.device) if want_ids else None
+    m64 = 2 ** 64 - 1
+    aug().augment_batch(v[0].data_ptr(), v[3].data_ptr(), B, _ptr(sym), int(seed) & m64,
+                        int(seq) & m64, int(board0) & m64, _ptr(ids), stream_handle())
+    return ids
+
+
 def policy_ensemble(logp: torch.Tensor, stones: torch.Tensor | None = None,
                     extra_illegal: torch.Tensor | None = None,
                     labels: torch.Tensor | None = None, S: int = 8, K: int = 5,

@@ -1,9 +1,10 @@
 """Loading of the in-tree native extensions.
 
-``hip()`` returns the ``_dghip`` module (CDNA4 kernels).  On a machine with a GPU a
-missing or stale extension is a hard error — there is deliberately no silent PyTorch
-fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
-SGF parser, loader thread pool).  Both are built by ``python -m deep_go_amd._build``
+``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
+(the batch-augmentation kernel), imported only when augmentation is asked for.  On a machine
+with a GPU a missing or stale extension is a hard error — there is deliberately no silent
+PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
+SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
 (also run by ``__graft_entry__.build()``); set ``DG_AUTOBUILD=1`` to build on first use.
 """
 from __future__ import annotations
@@ -33,7 +34,8 @@ def _load(name: str):
     except ImportError as e:
         if os.environ.get("DG_AUTOBUILD", "0") == "1":
             from .. import _build
-            {"_dghip": _build.build_hip, "_dgcomm": _build.build_comm}.get(
+            {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
+             "_dgcomm": _build.build_comm}.get(
                 name, _build.build_cpu)()
             mod = importlib.import_module(name)
         else:
@@ -46,6 +48,11 @@ def _load(name: str):
 
 def hip():
     return _load("_dghip")
+
+
+def aug():
+    """_dgaug: on-device D4 batch augmentation (csrc/kernels/augment.hip)."""
+    return _load("_dgaug")
 
 
 def cpu():

@@ -8,6 +8,12 @@ Both expose the same small surface used by the training loop:
   loss_sum() / correct()     of the last forward (host floats; synchronising)
   params / rate / state_dict / load_state_dict
 
+``load_next(loader)`` feeds the next training batch; with ``cfg.augment == "d4"`` it moves every
+board by the symmetry ``data/symmetry.py augment_symmetries(cfg.seed, seq, board0 + i)`` draws
+for it (``seq``: the batch's loader sequence number, ``board0``: this rank's first board in the
+global batch) — the numpy oracle on the CPU, the in-place kernel of augment.hip on the GPU, the
+same bytes either way.  ``set_batch`` (validation, eval, predict) is never augmented.
+
 * ``CPUBackend`` — fp32 PyTorch on the CPU (the reference's useCuda=false path,
   experiments.lua:97; also the numerical oracle).  DP over gloo.
 * ``HIPBackend`` — the MI355X executor (models/hip_model.py) with hipGraph replay and, for
@@ -36,10 +42,23 @@ def _np(x, dtype):
     return np.asarray(x, dtype=dtype)
 
 
+def augment_host_batch(cfg: ExperimentConfig, batch, seq: int, board0: int):
+    """A host batch (planes, player, rank, labels) as the net sees it at loader sequence
+    number ``seq``: unchanged for ``augment=none``, moved by the numpy oracle for ``d4``."""
+    if cfg.augment == "none" or batch is None:
+        return batch
+    from ..data.symmetry import augment_batch, augment_symmetries
+    planes, player, rank, labels = batch
+    planes, labels = augment_batch(planes, labels,
+                                   augment_symmetries(cfg.seed, seq, board0, len(labels)))
+    return planes, player, rank, labels
+
+
 class CPUBackend:
     def __init__(self, cfg: ExperimentConfig, batch: int, flat: Optional[torch.Tensor] = None,
-                 world: int = 1, bucket_mb: float = 4.0):
+                 world: int = 1, bucket_mb: float = 4.0, board0: int = 0):
         self.cfg = cfg
+        self.board0 = board0
         self.layout = ParamLayout(cfg)
         self.B = batch
         self.world = world
@@ -67,7 +86,8 @@ class CPUBackend:
         return self.opt.rate
 
     def load_next(self, loader):
-        batch = loader.next_numpy()
+        seq = loader.consumed          # the sequence number of the batch about to be taken
+        batch = augment_host_batch(self.cfg, loader.next_numpy(), seq, self.board0)
         self.set_batch(*batch)
         return batch
 
@@ -157,9 +177,10 @@ class CPUBackend:
 class HIPBackend:
     def __init__(self, cfg: ExperimentConfig, batch: int, flat: Optional[torch.Tensor] = None,
                  world: int = 1, device=None, use_graphs: bool = True, bucket_mb: float = 4.0,
-                 grad_dtype: str = "fp32", comm: str = "auto"):
+                 grad_dtype: str = "fp32", comm: str = "auto", board0: int = 0):
         from ..models.hip_model import HipGoNet, SegmentedStep
         self.cfg = cfg
+        self.board0 = board0
         self.B = batch
         self.world = world
         self.device = device or torch.device("cuda", torch.cuda.current_device())
@@ -187,6 +208,9 @@ class HIPBackend:
         # (HipGoNet.enable_prefetch; +1.1% with host batches, DG_PREFETCH=0: off)
         if os.environ.get("DG_PREFETCH", "auto") != "0":
             self.net.enable_prefetch()
+        self.augment = cfg.augment != "none"
+        if self.augment:
+            self.net.set_augment(cfg.seed, board0)
         self._step = SegmentedStep(self.net, self.bucketer, use_graphs=use_graphs)
         self._eval_n = batch
         self._last = "train"
@@ -202,8 +226,10 @@ class HIPBackend:
     def load_next(self, loader):
         """Next training batch straight from the loader's pinned packed slot into the
         network's input buffer: one async H2D copy, ordered before the step on the same
-        stream.  Returns None (the host copy is gone; ``current_batch`` reads it back)."""
-        self.net.set_batch_packed_from(loader)
+        stream.  With augmentation the kernel moves the boards right behind that copy, on the
+        same stream.  Returns None (the host copy is gone; ``current_batch`` reads it back)."""
+        self.net.set_batch_packed_from(loader,
+                                       aug_seq=loader.consumed if self.augment else None)
         return None
 
     def current_batch(self):

@@ -91,11 +91,13 @@ class Experiment:
             from .backends import HIPBackend
             self.backend = HIPBackend(cfg, self.local_batch, flat=self._restore_params,
                                       world=world, bucket_mb=cfg.bucket_mb,
-                                      grad_dtype=cfg.grad_dtype, comm=cfg.comm)
+                                      grad_dtype=cfg.grad_dtype, comm=cfg.comm,
+                                      board0=info.rank * self.local_batch)
         else:
             from .backends import CPUBackend
             self.backend = CPUBackend(cfg, self.local_batch, flat=self._restore_params,
-                                      world=world, bucket_mb=cfg.bucket_mb)
+                                      world=world, bucket_mb=cfg.bucket_mb,
+                                      board0=info.rank * self.local_batch)
             if world > 1 and self._restore_params is None:
                 dp.broadcast_(self.backend.params.data, 0)
         if self._restore_opt is not None:
@@ -114,7 +116,8 @@ class Experiment:
     def _regenerate_batch(self, seq):
         """The training batch the loader produced at sequence number ``seq`` (the loader is
         deterministic per (seed, rank, sequence): a fresh one started at ``seq`` yields the
-        same batch), or None."""
+        same batch) as the net saw it (moved by the same symmetries under ``augment=d4``), or
+        None."""
         if seq is None:
             return None
         try:
@@ -123,7 +126,9 @@ class Experiment:
                              seed=c.seed * 1000003 + self.info.rank, sampling=c.sampling,
                              start_seq=seq, pin=False)
             try:
-                return ld.next_numpy()
+                from .backends import augment_host_batch
+                return augment_host_batch(c, ld.next_numpy(), seq,
+                                          self.info.rank * self.local_batch)
             finally:
                 ld.close()
         except Exception:  # noqa: BLE001  (the dump is best effort; the raise is what matters)
