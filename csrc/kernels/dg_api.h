@@ -309,4 +309,15 @@ hipError_t dg_augment_batch(uint8_t* planes, int* labels, int B, const uint8_t* 
 int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
                         unsigned long long board);
 
+// ---------------------------------------------------------------- optim.hip (module _dgopt)
+// SGD with momentum over the flat vector, one launch: gi = g * gscale; gw = gi + wd * p inside
+// a decay range, else gi; v = mu * v + gw; p -= lr * (nesterov ? gw + mu * v : v).  ranges: a
+// HOST array of n_ranges <= 20 rows {begin, end} (elements; sorted, disjoint, non-empty, begin
+// a multiple of 64, end <= n and below 2^32 - 1), passed to the kernel by value.  gate / g16
+// as dg_sgd; p, v, g 16-byte aligned (g16: 8).  lr is read, not written: the decay stays with
+// dg_weight_refresh.
+hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const double* lr, float mu,
+                       int nesterov, float wd, const long long* ranges, int n_ranges,
+                       float gscale, const float* gate, const void* g16, hipStream_t s);
+
 }  // extern "C"

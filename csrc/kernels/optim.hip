@@ -1,0 +1,162 @@
+// SGD with momentum, Nesterov and weight decay over the flat fp32 master vector (module _dgopt,
+// opt_bindings.cpp; loaded only for optimizer=momentum, so the interface of _dghip stays as
+// recorded).  deep_go_amd/train/optim.py Momentum is the definition; per element i
+//
+//   gi = g[i] * gscale
+//   gw = gi + wd * p[i]          if i lies in a decay range (the conv weights), else gi
+//   v[i] = mu * v[i] + gw
+//   u  = gw + mu * v[i]          if nesterov, else v[i]          (v[i]: the new value)
+//   p[i] -= lr * u
+//
+// which is torch.optim.SGD(momentum, dampening 0, nesterov, weight_decay) with the learning
+// rate outside the velocity.  The LR decay and the operand refresh stay with weight_refresh.
+#include "dg_api.h"
+#include "dg_common.h"
+
+using namespace dg;
+
+namespace {
+
+constexpr int MAX_RANGES = 20;   // elementwise.hip MAX_GU: one range per layer
+constexpr int RANGE_ALIGN = 64;  // models/gocnn.py ALIGN: every tensor's first element
+constexpr int MT = 256;          // threads per workgroup; one 4-vector per thread and pass
+// the grid's cap: one pass per workgroup up to 8.4 M elements (12x256 has 7.2 M).  Measured at
+// 12x256 against rmsprop: caps of 2048 (two vectors per thread) / 4096 / 8192 gave +0.58 /
+// +0.35 / -0.28 us (profiles/opt_momentum.txt)
+constexpr int MAX_BLOCKS = 8192;
+
+// The decay ranges [b, e), sorted and disjoint, b a multiple of RANGE_ALIGN, as 32-bit element
+// indices: by value in the kernel arguments (scalar loads, no scratch copy).  Unused rows hold
+// NO_RANGE twice: they end after every chunk and begin inside none.
+constexpr unsigned NO_RANGE = 0xFFFFFFFFu;
+struct DecayRanges {
+  unsigned b[MAX_RANGES];
+  unsigned e[MAX_RANGES];
+};
+
+// as elementwise.hip: gradient 4-vector i4 from the flat fp32 gradient (16-byte load) or from
+// its bf16 wire twin (8-byte load).  The raw bits are loaded first and widened only where the
+// update needs them, so the wait for the load comes after the mask is found.
+DG_DEV float grad_at(const float* g, size_t i) { return g[i]; }
+DG_DEV float grad_at(const bf16_t* g, size_t i) { return bf2f(g[i]); }
+DG_DEV f32x4 grad4_raw(const float* g, size_t i4) { return ((const f32x4*)g)[i4]; }
+DG_DEV uint2 grad4_raw(const bf16_t* g, size_t i4) { return ((const uint2*)g)[i4]; }
+DG_DEV f32x4 grad4_f32(const f32x4 raw) { return raw; }
+DG_DEV f32x4 grad4_f32(const uint2 u) {
+  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
+               __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
+}
+
+// one element (and, with T = f32x4, one 4-vector): w = wd inside a decay range, else 0
+template <typename T>
+DG_DEV void momentum_update(T& p, T& v, const T g, const T w, float l, float mu, float gscale,
+                            bool nesterov) {
+  const T gw = g * gscale + w * p;
+  v = mu * v + gw;
+  p -= l * (nesterov ? gw + mu * v : v);
+}
+
+// One pass of a workgroup covers MT consecutive 4-vectors (a wave's loads are contiguous).
+// Its loads are issued first; while they are in flight the workgroup finds the chunk's decay
+// mask.  The chunk's position is uniform, so this is scalar work: the ends e[] sit in scalar
+// registers (compile-time positions), r = how many ranges end at or before the chunk is a sum
+// of 20 compares with no load behind it, and only the ranges from r on that begin inside the
+// chunk (almost always one) are compared per element, as 32-bit offsets from the chunk's
+// first element.  A range's end is no multiple of 4 in general, hence per element.
+template <typename G>
+__global__ void __launch_bounds__(MT)
+momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ v, size_t n,
+                const double* __restrict__ lr, float mu, int nesterov, float wd,
+                const DecayRanges R, float gscale, const float* __restrict__ gate) {
+  // gate 0 skips the update (sgd_kernel): return before any access
+  if (gate && *gate == 0.f) return;
+  const float l = (float)(*lr);
+  const bool nes = nesterov != 0;
+  const size_t n4 = n / 4;
+  constexpr int CE = MT * 4;          // elements per workgroup and pass
+  const int tid = threadIdx.x;
+  for (size_t c0 = blockIdx.x * (size_t)MT; c0 < n4; c0 += (size_t)gridDim.x * MT) {
+    const size_t i = c0 + tid;
+    const bool live = i < n4;
+    f32x4 pv, vv;
+    decltype(grad4_raw(g, 0)) gv;
+    if (live) {
+      pv = ((const f32x4*)p)[i];
+      vv = ((const f32x4*)v)[i];
+      gv = grad4_raw(g, i);
+    }
+    // the chunk [e0, e1) in elements, saturated: every range lies below 2^32 - 1
+    const size_t c4 = c0 * 4;
+    const unsigned e0 = c4 < NO_RANGE ? (unsigned)c4 : NO_RANGE;
+    const unsigned e1 = c4 + CE < NO_RANGE ? (unsigned)(c4 + CE) : NO_RANGE;
+    int r = 0;
+#pragma unroll
+    for (int q = 0; q < MAX_RANGES; ++q) r += R.e[q] <= e0 ? 1 : 0;
+    f32x4 w = {0.f, 0.f, 0.f, 0.f};
+    for (int q = r; q < MAX_RANGES && R.b[q] < e1; ++q) {
+      // [lo, hi): the range in elements from the chunk's first, clipped to the chunk
+      const int lo = R.b[q] > e0 ? (int)(R.b[q] - e0) : 0;
+      const int hi = R.e[q] < e1 ? (int)(R.e[q] - e0) : CE;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (tid * 4 + j >= lo && tid * 4 + j < hi) w[j] = wd;
+    }
+    if (live) {
+      momentum_update(pv, vv, grad4_f32(gv), w, l, mu, gscale, nes);
+      ((f32x4*)v)[i] = vv;
+      ((f32x4*)p)[i] = pv;
+    }
+  }
+  // the n % 4 tail: at most three elements, one lane each
+  const size_t i = n4 * 4 + tid;
+  if (blockIdx.x == 0 && i < n) {
+    float w = 0.f;
+    for (int q = 0; q < MAX_RANGES; ++q)
+      if (i >= R.b[q] && i < R.e[q]) w = wd;
+    float pi = p[i], vi = v[i];
+    momentum_update(pi, vi, grad_at(g, i), w, l, mu, gscale, nes);
+    v[i] = vi;
+    p[i] = pi;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const double* lr, float mu,
+                       int nesterov, float wd, const long long* ranges, int n_ranges,
+                       float gscale, const float* gate, const void* g16, hipStream_t s) {
+  if (n_ranges < 0 || n_ranges > MAX_RANGES || (n_ranges && !ranges))
+    return hipErrorInvalidValue;
+  DecayRanges R;
+  long long prev = 0;
+  for (int q = 0; q < MAX_RANGES; ++q) {
+    R.b[q] = R.e[q] = NO_RANGE;
+    if (q >= n_ranges) continue;
+    const long long b = ranges[2 * q], e = ranges[2 * q + 1];
+    if (b < prev || b % RANGE_ALIGN != 0 || e <= b || (unsigned long long)e > n ||
+        e >= (long long)NO_RANGE)
+      return hipErrorInvalidValue;
+    R.b[q] = (unsigned)b;
+    R.e[q] = (unsigned)e;
+    prev = e;
+  }
+  if (n == 0) return hipSuccess;
+  if (!p || !v || !lr || !(g || g16)) return hipErrorInvalidValue;
+  // the 16-byte (bf16: 8-byte) vector accesses
+  if ((((uintptr_t)p | (uintptr_t)v | (uintptr_t)g) & 15) || ((uintptr_t)g16 & 7))
+    return hipErrorInvalidValue;
+  size_t blocks = (n / 4 + MT - 1) / MT;
+  if (blocks > MAX_BLOCKS) blocks = MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  if (g16)
+    hipLaunchKernelGGL(momentum_kernel<bf16_t>, dim3((unsigned)blocks), dim3(MT), 0, s, p,
+                       (const bf16_t*)g16, v, n, lr, mu, nesterov, wd, R, gscale, gate);
+  else
+    hipLaunchKernelGGL(momentum_kernel<float>, dim3((unsigned)blocks), dim3(MT), 0, s, p, g, v,
+                       n, lr, mu, nesterov, wd, R, gscale, gate);
+  return hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,11 +1,12 @@
 """In-tree native build: hipcc for the gfx950 kernels, g++ for the CPU engine.
 
 Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
-``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module) and
+``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module),
+``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|cpu|comm]
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -83,15 +84,14 @@ def build_hip(force: bool = False, jobs: int = 8) -> Path:
     return target
 
 
-def build_aug(force: bool = False) -> Path:
-    """_dgaug: the training-time symmetry augmentation (augment.hip + its two bindings), apart
-    from _dghip so that module's recorded interface stays as it is."""
+def _build_small(name: str, kernel: str, binding: str, force: bool) -> Path:
+    """A module of one kernel file and its bindings (objects build/<name>_<source>.o)."""
     BUILD.mkdir(exist_ok=True)
     OUT.mkdir(exist_ok=True)
-    target = OUT / f"_dgaug{EXT}"
+    target = OUT / f"_dg{name}{EXT}"
     headers = list(KDIR.glob("*.h"))
-    kern, kobj = KDIR / "augment.hip", BUILD / "aug_augment.hip.o"
-    bind, bobj = KDIR / "aug_bindings.cpp", BUILD / "aug_bindings.cpp.o"
+    kern, kobj = KDIR / kernel, BUILD / f"{name}_{kernel}.o"
+    bind, bobj = KDIR / binding, BUILD / f"{name}_{binding}.o"
     built = False
     if force or _newer(kern, kobj, headers):
         _run([HIPCC, *HIP_FLAGS, "-c", str(kern), "-o", str(kobj)])
@@ -104,6 +104,18 @@ def build_aug(force: bool = False) -> Path:
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "--hip-link", "-o",
               str(target), str(kobj), str(bobj)])
     return target
+
+
+def build_aug(force: bool = False) -> Path:
+    """_dgaug: the training-time symmetry augmentation (augment.hip + its two bindings), apart
+    from _dghip so that module's recorded interface stays as it is."""
+    return _build_small("aug", "augment.hip", "aug_bindings.cpp", force)
+
+
+def build_opt(force: bool = False) -> Path:
+    """_dgopt: SGD with momentum / Nesterov / weight decay (optim.hip + its two bindings),
+    apart from _dghip for the same reason."""
+    return _build_small("opt", "optim.hip", "opt_bindings.cpp", force)
 
 
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
@@ -159,13 +171,14 @@ def build_all(force: bool = False) -> None:
     build_cpu(force)
     build_hip(force)
     build_aug(force)
+    build_opt(force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "opt", "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -175,6 +188,8 @@ def main(argv=None):
         print(build_hip(a.force, a.j))
     if a.only in (None, "aug") and not a.sanitize:
         print(build_aug(a.force))
+    if a.only in (None, "opt") and not a.sanitize:
+        print(build_opt(a.force))
     if a.only in (None, "comm") and not a.sanitize:
         print(build_comm(a.force))
 

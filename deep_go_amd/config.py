@@ -54,8 +54,13 @@ class ExperimentConfig:
     seed: int = 1234
     synthetic: bool = False        # synthetic boards instead of the on-disk dataset
     head_relu: bool = True         # reference applies ReLU to the head (parity)
-    optimizer: str = "sgd"         # sgd | rmsprop (the reference's misnamed AdagradOptimizer)
+    # sgd | rmsprop (the reference's misnamed AdagradOptimizer) | momentum (SGD with momentum,
+    # train/optim.py Momentum: the three fields below; they are rejected with sgd | rmsprop)
+    optimizer: str = "sgd"
     rmsprop_decay: float = 0.9
+    momentum: float = 0.9          # velocity decay mu, in [0, 1)
+    nesterov: bool = False         # step along gw + mu v instead of v
+    weight_decay: float = 0.0      # L2 coefficient on the conv weights (never on the biases)
     bucket_mb: float = 6.0         # DP gradient bucket size (12x128: head + hidden layers | layer 0)
     # DP all-reduce dtype: fp32 (the reference's DataParallelTable reduces fp32 gradients,
     # experiments.lua:155-168) | bf16 (opt-in: the wire twin every gradient pass 2 writes; half
@@ -175,7 +180,7 @@ def _coerce(name: str, value: Any, current: Any) -> Any:
 
 
 _CHOICES = {"nan_policy": ("guard", "skip", "raise"), "comm": ("auto", "native", "torch"),
-            "optimizer": ("sgd", "rmsprop"), "grad_dtype": ("fp32", "bf16"),
+            "optimizer": ("sgd", "rmsprop", "momentum"), "grad_dtype": ("fp32", "bf16"),
             "sampling": ("game", "position"), "augment": ("none", "d4")}
 
 
@@ -188,7 +193,16 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
     for k, v in vals.items():
         if k in _CHOICES and v not in _CHOICES[k]:
             raise ValueError(f"{k}={v!r}: expected one of {_CHOICES[k]}")
-    return dataclasses.replace(cfg, **vals)
+    new = dataclasses.replace(cfg, **vals)
+    if not 0.0 <= new.momentum < 1.0:
+        raise ValueError(f"momentum={new.momentum!r}: expected a value in [0, 1)")
+    if new.weight_decay < 0.0:
+        raise ValueError(f"weight_decay={new.weight_decay!r}: expected a value >= 0")
+    if new.optimizer != "momentum" and (new.nesterov or new.weight_decay != 0.0):
+        # (those two update paths have no such terms: do not ignore the setting silently)
+        raise ValueError(f"nesterov / weight_decay need optimizer=momentum, "
+                         f"not optimizer={new.optimizer!r}")
+    return new
 
 
 def parse_overrides(items: List[str]) -> Dict[str, Any]:

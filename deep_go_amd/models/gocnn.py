@@ -109,6 +109,12 @@ class ParamLayout:
             out.append((f"pos_bias{n}", L.pos_off, NUM_POINTS * L.cout))
         return out
 
+    def weight_ranges(self) -> List[Tuple[int, int]]:
+        """[begin, end) of every layer's conv weights (the head's included) in flat order:
+        what weight decay applies to.  The per-channel and per-position biases and the
+        alignment padding lie outside."""
+        return [(L.w_off, L.w_off + L.w_numel) for L in self.layers]
+
     def layer_range(self, i: int) -> Tuple[int, int]:
         """[start, end) of layer i's parameters in the flat buffer (aligned)."""
         start = self.layers[i].w_off

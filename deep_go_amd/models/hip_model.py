@@ -30,7 +30,7 @@ import torch
 from ..config import NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import hip, stream_handle
+from ..ops.native import hip, opt, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -223,6 +223,20 @@ class HipGoNet:
         self.ms = None
         if cfg.optimizer == "rmsprop":
             self.ms = torch.ones_like(self.params)
+        # optimizer=momentum: the velocity, and the kernel's module (_dgopt: optim.hip) with
+        # the table of conv-weight ranges that weight decay applies to
+        self.vel = None
+        if cfg.optimizer == "momentum":
+            self.vel = torch.zeros_like(self.params)
+            self._opt = opt()
+            self._wd_ranges = np.ascontiguousarray(
+                np.array(self.layout.weight_ranges(), dtype=np.int64))
+            # one launch behind a closed gate (it returns at once): the module's code object
+            # is loaded here, not inside the capture of a step graph
+            self._opt.momentum(self.params.data_ptr(), self.grads.data_ptr(),
+                               self.vel.data_ptr(), self.params.numel(), self.lr.data_ptr(),
+                               0.0, 0, 0.0, self._wd_ranges.ctypes.data, len(self._wd_ranges),
+                               1.0, torch.zeros(1, device=dev).data_ptr(), stream_handle())
         # non-finite loss guard (cfg.nan_policy == "skip"): device gate read by the optimizer
         self.gate = torch.ones(1, dtype=torch.float32, device=dev)
         self._gate_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # finite_gate1
@@ -1398,8 +1412,9 @@ class HipGoNet:
         needs the reduced gradient; the bf16 wire twin is a DP format), no gradient hooks, and
         every layer's slabs / partials in buffers of their own: one grouped weight-gradient
         launch, plus at most the first layer's own chain.  DG_FUSED_UPDATE=0: never (and the
-        optimizer keeps the separate SGD + refresh launches)."""
-        if not self.knobs.FUSED_UPDATE:
+        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum: never (its
+        update is a launch of its own, not part of grad_update)."""
+        if not self.knobs.FUSED_UPDATE or self.vel is not None:
             return False
         if self.global_batch != self.B or self.grads16 is not None or self.grad_hooks:
             return False
@@ -1491,8 +1506,14 @@ class HipGoNet:
         self._gate_issued = False
         if not (slabs and self._early_issued):
             self._fp8_update(s)
-        if not self.knobs.FUSED_UPDATE:
-            if self.ms is not None:
+        if not self.knobs.FUSED_UPDATE or self.vel is not None:
+            if self.vel is not None:
+                r = self._wd_ranges
+                (self._opt.momentum_bf16 if w16 else self._opt.momentum)(
+                    self.params.data_ptr(), g, self.vel.data_ptr(), n, self.lr.data_ptr(),
+                    float(self.cfg.momentum), int(self.cfg.nesterov),
+                    float(self.cfg.weight_decay), r.ctypes.data, len(r), grad_scale, gate, s)
+            elif self.ms is not None:
                 (self.h.rmsprop_bf16 if w16 else self.h.rmsprop)(
                     self.params.data_ptr(), g, self.ms.data_ptr(), n, self.lr.data_ptr(),
                     float(self.cfg.rmsprop_decay), grad_scale, gate, s)

@@ -409,6 +409,22 @@ def augment_batch(buf: torch.Tensor, B: int, sym: torch.Tensor | None = None, se
     return ids
 
 
+def momentum_(p: torch.Tensor, g: torch.Tensor, v: torch.Tensor, lr: torch.Tensor, mu: float,
+              nesterov: bool = False, wd: float = 0.0, ranges=(), gscale: float = 1.0,
+              gate: torch.Tensor | None = None):
+    """One momentum step in place on the device vectors p, v (fp32) from the gradient g (fp32,
+    or bf16: the wire twin) — optim.hip; ``lr`` the device double, ``ranges`` the [begin, end)
+    pairs weight decay applies to, ``gate`` an optional device float (0 skips the update)."""
+    from .native import opt
+    n = p.numel()
+    assert v.numel() == n and g.numel() == n and lr.dtype == torch.float64
+    r = np.ascontiguousarray(np.array(list(ranges), dtype=np.int64).reshape(-1, 2))
+    fn = opt().momentum_bf16 if g.dtype == torch.bfloat16 else opt().momentum
+    fn(p.data_ptr(), g.data_ptr(), v.data_ptr(), n, lr.data_ptr(), float(mu), int(nesterov),
+       float(wd), r.ctypes.data if len(r) else 0, len(r), float(gscale), _ptr(gate),
+       stream_handle())
+
+
 def policy_ensemble(logp: torch.Tensor, stones: torch.Tensor | None = None,
                     extra_illegal: torch.Tensor | None = None,
                     labels: torch.Tensor | None = None, S: int = 8, K: int = 5,

@@ -1,7 +1,8 @@
 """Loading of the in-tree native extensions.
 
 ``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
-(the batch-augmentation kernel), imported only when augmentation is asked for.  On a machine
+(the batch-augmentation kernel), imported only when augmentation is asked for; ``opt()`` the
+``_dgopt`` module (the momentum optimizer's kernel), imported only for it.  On a machine
 with a GPU a missing or stale extension is a hard error — there is deliberately no silent
 PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
 SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
@@ -35,7 +36,7 @@ def _load(name: str):
         if os.environ.get("DG_AUTOBUILD", "0") == "1":
             from .. import _build
             {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
-             "_dgcomm": _build.build_comm}.get(
+             "_dgopt": _build.build_opt, "_dgcomm": _build.build_comm}.get(
                 name, _build.build_cpu)()
             mod = importlib.import_module(name)
         else:
@@ -53,6 +54,11 @@ def hip():
 def aug():
     """_dgaug: on-device D4 batch augmentation (csrc/kernels/augment.hip)."""
     return _load("_dgaug")
+
+
+def opt():
+    """_dgopt: SGD with momentum / Nesterov / weight decay (csrc/kernels/optim.hip)."""
+    return _load("_dgopt")
 
 
 def cpu():

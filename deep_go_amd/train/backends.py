@@ -3,7 +3,7 @@
 Both expose the same small surface used by the training loop:
   set_batch(planes uint8 [B,9,19,19], player, rank, labels)   (host numpy or tensors)
   forward_backward()         loss/argmax of the batch + gradients (global-batch mean)
-  optimizer_step()           SGD/RMSProp + per-step LR decay
+  optimizer_step()           SGD/RMSProp/Momentum + per-step LR decay
   evaluate(n)                forward only on the first n boards of the current batch
   loss_sum() / correct()     of the last forward (host floats; synchronising)
   params / rate / state_dict / load_state_dict
@@ -33,7 +33,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, RMSProp
+from .optim import SGD, Momentum, RMSProp
 
 
 def _np(x, dtype):
@@ -67,6 +67,10 @@ class CPUBackend:
         self.params.requires_grad_(True)
         if cfg.optimizer == "rmsprop":
             self.opt = RMSProp(cfg.rate, cfg.rmsprop_decay, self.layout.numel)
+        elif cfg.optimizer == "momentum":
+            self.opt = Momentum(cfg.rate, cfg.rateDecay, cfg.momentum, cfg.nesterov,
+                                cfg.weight_decay, self.layout.numel,
+                                self.layout.weight_ranges())
         else:
             self.opt = SGD(cfg.rate, cfg.rateDecay)
         self._x = None
@@ -297,6 +301,8 @@ class HIPBackend:
                            "rate_decay": self.cfg.rateDecay}}
         if self.net.ms is not None:
             d["optimizer"]["ms"] = self.net.ms.detach().cpu()
+        if self.net.vel is not None:
+            d["optimizer"]["vel"] = self.net.vel.detach().cpu()
         return d
 
     def close(self):
@@ -310,3 +316,9 @@ class HIPBackend:
         self.net.lr.fill_(float(o["rate"]))
         if "ms" in o and self.net.ms is not None:
             self.net.ms.copy_(o["ms"].to(self.net.ms.device))
+        if self.net.vel is not None:
+            # (a checkpoint without a velocity: start from rest)
+            if "vel" in o:
+                self.net.vel.copy_(o["vel"].to(self.net.vel.device))
+            else:
+                self.net.vel.zero_()
