@@ -415,7 +415,7 @@ extern "C" hipError_t dg_head(int kw, const void* X, int x_pad, int C, int B, co
                               float* loss, int* pred, float* logp_out, void* dZ, int dz_pad,
                               float* gw_part, float* unused, float* dzb, int head_relu,
                               float grad_scale, hipStream_t stream) {
-  if (C % 8 != 0 || B <= 0) return hipErrorInvalidValue;
+  if (C <= 0 || C % 8 != 0 || B <= 0) return hipErrorInvalidValue;
   // 3x3 head over a 128/256-channel pad-1 frame: the MFMA kernel (head_mfma.hip)
   if (kw == 3 && (C == 128 || C == 256) && x_pad == 1 && (!dZ || dz_pad == 1))
     return dg_head_mfma(C, X, B, w, bias, posb, labels, loss, pred, logp_out, dZ, gw_part, dzb,
@@ -428,6 +428,9 @@ extern "C" hipError_t dg_head(int kw, const void* X, int x_pad, int C, int B, co
   const int cc = C < CCH ? C : CCH;
   const size_t lds = (size_t)((F * F * (cc / 8) + 63) / 64) * 64 * 16 +
                      (size_t)(kw * kw * C + 384 + 384 + kw * kw * CCH + HT) * 4 + HT * 4;
+  // a 5x5 head at C >= 128 does not fit the CU's 160 KB: refuse it here (allow_lds_once
+  // drops the attribute call's result, the launch would report whatever it makes of it)
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
   switch (kw) {
     case 1:
       allow_lds_once(head_kernel<1>, lds);
