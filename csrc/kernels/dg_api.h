@@ -309,7 +309,7 @@ hipError_t dg_augment_batch(uint8_t* planes, int* labels, int B, const uint8_t* 
 int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
                         unsigned long long board);
 
-// ---------------------------------------------------------------- optim.hip (module _dgopt)
+// ------------------------------------------------- optim.hip (modules _dgopt and _dgadam)
 // SGD with momentum over the flat vector, one launch: gi = g * gscale; gw = gi + wd * p inside
 // a decay range, else gi; v = mu * v + gw; p -= lr * (nesterov ? gw + mu * v : v).  ranges: a
 // HOST array of n_ranges <= 20 rows {begin, end} (elements; sorted, disjoint, non-empty, begin
@@ -319,5 +319,19 @@ int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
 hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const double* lr, float mu,
                        int nesterov, float wd, const long long* ranges, int n_ranges,
                        float gscale, const float* gate, const void* g16, hipStream_t s);
+
+// AdamW over the flat vector (module _dgadam): gi = g * gscale; m = beta1 m + (1 - beta1) gi;
+// v = beta2 v + (1 - beta2) gi^2; p *= 1 - lr wd inside a decay range; p -= lr c1 m /
+// (sqrt(v) c2 + eps).  rec: the optimizer's 16-byte device record {int64 t; float c1; float c2}
+// (8-byte aligned), t the count of APPLIED steps.  Two launches on s: dg_adamw_tick (one wave:
+// behind an open gate t += 1, c1 = 1 / (1 - beta1^t), c2 = 1 / sqrt(1 - beta2^t), in double;
+// nothing behind a closed one), then the update, which only reads c1 and c2.  gate 0 leaves p,
+// m, v and rec untouched.  ranges, gate, g16, lr and the alignment of p, m, v, g as
+// dg_momentum; beta1, beta2 in [0, 1), eps > 0.
+hipError_t dg_adamw_tick(void* rec, float beta1, float beta2, const float* gate, hipStream_t s);
+hipError_t dg_adamw(float* p, const float* g, float* m, float* v, size_t n, const double* lr,
+                    void* rec, float beta1, float beta2, float eps, float wd,
+                    const long long* ranges, int n_ranges, float gscale, const float* gate,
+                    const void* g16, hipStream_t s);
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 // stays as recorded.  Conventions as in bindings.cpp: tensors cross as raw device addresses,
 // the range table as the address of a host int64 array, the stream as its handle; a launcher's
 // error becomes RuntimeError("<name>: <hipGetErrorString>").  dg_api.h declares dg_momentum.
+// optim.hip also holds AdamW (dg_adamw); that is bound in adam_bindings.cpp (module `_dgadam`),
+// because this module's public names are pinned to the two below.
 #include <pybind11/pybind11.h>
 
 #include <stdexcept>

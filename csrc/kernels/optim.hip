@@ -1,6 +1,8 @@
-// SGD with momentum, Nesterov and weight decay over the flat fp32 master vector (module _dgopt,
-// opt_bindings.cpp; loaded only for optimizer=momentum, so the interface of _dghip stays as
-// recorded).  deep_go_amd/train/optim.py Momentum is the definition; per element i
+// The optimizers with a launch of their own over the flat fp32 master vector: SGD with momentum,
+// Nesterov and weight decay (dg_momentum: module _dgopt, opt_bindings.cpp, loaded only for
+// optimizer=momentum) and AdamW (dg_adamw, further down: module _dgadam, adam_bindings.cpp,
+// loaded only for optimizer=adamw).  Neither is part of _dghip, so its interface stays as
+// recorded.  deep_go_amd/train/optim.py Momentum is the definition; per element i
 //
 //   gi = g[i] * gscale
 //   gw = gi + wd * p[i]          if i lies in a decay range (the conv weights), else gi
@@ -47,6 +49,42 @@ DG_DEV f32x4 grad4_f32(const uint2 u) {
                __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
 }
 
+// The decay mask of one workgroup pass: MT consecutive 4-vectors from 4-vector c0, thread tid's
+// four elements -> `in` inside a decay range, 0 elsewhere.  The chunk's position is uniform,
+// so this is scalar work: the ends e[] sit in scalar registers (compile-time positions), r = how
+// many ranges end at or before the chunk is a sum of 20 compares with no load behind it, and
+// only the ranges from r on that begin inside the chunk (almost always one) are compared per
+// element, as 32-bit offsets from the chunk's first element.  A range's end is no multiple of 4
+// in general, hence per element.
+constexpr int CE = MT * 4;          // elements per workgroup and pass
+DG_DEV f32x4 chunk_mask(const DecayRanges& R, size_t c0, int tid, float in) {
+  // the chunk [e0, e1) in elements, saturated: every range lies below 2^32 - 1
+  const size_t c4 = c0 * 4;
+  const unsigned e0 = c4 < NO_RANGE ? (unsigned)c4 : NO_RANGE;
+  const unsigned e1 = c4 + CE < NO_RANGE ? (unsigned)(c4 + CE) : NO_RANGE;
+  int r = 0;
+#pragma unroll
+  for (int q = 0; q < MAX_RANGES; ++q) r += R.e[q] <= e0 ? 1 : 0;
+  f32x4 w = {0.f, 0.f, 0.f, 0.f};
+  for (int q = r; q < MAX_RANGES && R.b[q] < e1; ++q) {
+    // [lo, hi): the range in elements from the chunk's first, clipped to the chunk
+    const int lo = R.b[q] > e0 ? (int)(R.b[q] - e0) : 0;
+    const int hi = R.e[q] < e1 ? (int)(R.e[q] - e0) : CE;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (tid * 4 + j >= lo && tid * 4 + j < hi) w[j] = in;
+  }
+  return w;
+}
+
+// the same for one element of the n % 4 tail
+DG_DEV float tail_mask(const DecayRanges& R, size_t i, float in) {
+  float w = 0.f;
+  for (int q = 0; q < MAX_RANGES; ++q)
+    if (i >= R.b[q] && i < R.e[q]) w = in;
+  return w;
+}
+
 // one element (and, with T = f32x4, one 4-vector): w = wd inside a decay range, else 0
 template <typename T>
 DG_DEV void momentum_update(T& p, T& v, const T g, const T w, float l, float mu, float gscale,
@@ -58,11 +96,7 @@ DG_DEV void momentum_update(T& p, T& v, const T g, const T w, float l, float mu,
 
 // One pass of a workgroup covers MT consecutive 4-vectors (a wave's loads are contiguous).
 // Its loads are issued first; while they are in flight the workgroup finds the chunk's decay
-// mask.  The chunk's position is uniform, so this is scalar work: the ends e[] sit in scalar
-// registers (compile-time positions), r = how many ranges end at or before the chunk is a sum
-// of 20 compares with no load behind it, and only the ranges from r on that begin inside the
-// chunk (almost always one) are compared per element, as 32-bit offsets from the chunk's
-// first element.  A range's end is no multiple of 4 in general, hence per element.
+// mask (chunk_mask).
 template <typename G>
 __global__ void __launch_bounds__(MT)
 momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ v, size_t n,
@@ -73,7 +107,6 @@ momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restric
   const float l = (float)(*lr);
   const bool nes = nesterov != 0;
   const size_t n4 = n / 4;
-  constexpr int CE = MT * 4;          // elements per workgroup and pass
   const int tid = threadIdx.x;
   for (size_t c0 = blockIdx.x * (size_t)MT; c0 < n4; c0 += (size_t)gridDim.x * MT) {
     const size_t i = c0 + tid;
@@ -85,22 +118,7 @@ momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restric
       vv = ((const f32x4*)v)[i];
       gv = grad4_raw(g, i);
     }
-    // the chunk [e0, e1) in elements, saturated: every range lies below 2^32 - 1
-    const size_t c4 = c0 * 4;
-    const unsigned e0 = c4 < NO_RANGE ? (unsigned)c4 : NO_RANGE;
-    const unsigned e1 = c4 + CE < NO_RANGE ? (unsigned)(c4 + CE) : NO_RANGE;
-    int r = 0;
-#pragma unroll
-    for (int q = 0; q < MAX_RANGES; ++q) r += R.e[q] <= e0 ? 1 : 0;
-    f32x4 w = {0.f, 0.f, 0.f, 0.f};
-    for (int q = r; q < MAX_RANGES && R.b[q] < e1; ++q) {
-      // [lo, hi): the range in elements from the chunk's first, clipped to the chunk
-      const int lo = R.b[q] > e0 ? (int)(R.b[q] - e0) : 0;
-      const int hi = R.e[q] < e1 ? (int)(R.e[q] - e0) : CE;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (tid * 4 + j >= lo && tid * 4 + j < hi) w[j] = wd;
-    }
+    const f32x4 w = chunk_mask(R, c0, tid, wd);
     if (live) {
       momentum_update(pv, vv, grad4_f32(gv), w, l, mu, gscale, nes);
       ((f32x4*)v)[i] = vv;
@@ -110,9 +128,7 @@ momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restric
   // the n % 4 tail: at most three elements, one lane each
   const size_t i = n4 * 4 + tid;
   if (blockIdx.x == 0 && i < n) {
-    float w = 0.f;
-    for (int q = 0; q < MAX_RANGES; ++q)
-      if (i >= R.b[q] && i < R.e[q]) w = wd;
+    const float w = tail_mask(R, i, wd);
     float pi = p[i], vi = v[i];
     momentum_update(pi, vi, grad_at(g, i), w, l, mu, gscale, nes);
     v[i] = vi;
@@ -120,16 +136,119 @@ momentum_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------- AdamW
+// Adam with decoupled weight decay (deep_go_amd/train/optim.py AdamW is the definition).  Only
+// an APPLIED step counts: t is a device counter of the optimizer's own, which a skipped step
+// (gate 0) leaves alone, unlike step_count.  Per applied step, once:
+//
+//   t += 1;  c1 = 1 / (1 - beta1^t);  c2 = 1 / sqrt(1 - beta2^t)      (double, stored as fp32)
+//
+// and per element i
+//
+//   gi = g[i] * gscale
+//   m[i] = beta1 * m[i] + (1 - beta1) * gi
+//   v[i] = beta2 * v[i] + (1 - beta2) * gi * gi
+//   p[i] = p[i] * (1 - lr * wd)                       if i lies in a decay range
+//   p[i] = p[i] - (lr * c1) * m[i] / (sqrt(v[i]) * c2 + eps)
+//
+// which is torch.optim.AdamW(lr, betas, eps, weight_decay, amsgrad=False) with the decay ranges
+// as one parameter group and the rest as another.
+//
+// The count lives in a 16-byte device record.  No thread reads a count that a thread of the
+// same launch writes: adamw_tick, one wave, advances t and writes c1, c2 behind an open gate
+// (nothing behind a closed one); adamw_kernel, launched after it on the same stream, only reads
+// c1 and c2.  Stream order makes that race-free whatever the grid's size, and both launches are
+// captured together.
+struct AdamRecord {
+  long long t;
+  float c1, c2;
+};
+static_assert(sizeof(AdamRecord) == 16, "the record's layout is part of the interface");
+
+__global__ void __launch_bounds__(64)
+adamw_tick(AdamRecord* __restrict__ rec, float beta1, float beta2,
+           const float* __restrict__ gate) {
+  if (threadIdx.x != 0 || (gate && *gate == 0.f)) return;
+  const long long t = rec->t + 1;
+  // pow in double: beta^t underflows to 0 at large t, and both corrections become exactly 1
+  const double d1 = 1.0 - pow((double)beta1, (double)t);
+  const double d2 = 1.0 - pow((double)beta2, (double)t);
+  rec->t = t;
+  rec->c1 = (float)(1.0 / d1);
+  rec->c2 = (float)(1.0 / sqrt(d2));
+}
+
+// one element: lw = lr wd inside a decay range, else 0 (p * (1 - 0) is exact); lc = lr c1;
+// o1 = 1 - beta1, o2 = 1 - beta2.  `/` and sqrtf are the correctly rounded forms under the
+// build's flags (v_div_scale / v_div_fmas / v_div_fixup; v_sqrt_f32 and its two fma
+// corrections): clang's HIP default.  The kernel is bound by its 28 bytes per element.
+DG_DEV void adamw_update(float& p, float& m, float& v, float g, float lw, float lc, float b1,
+                         float o1, float b2, float o2, float c2, float eps, float gscale) {
+  const float gi = g * gscale;
+  m = b1 * m + o1 * gi;
+  v = b2 * v + (o2 * gi) * gi;
+  p = p * (1.f - lw) - (lc * m) / (sqrtf(v) * c2 + eps);
+}
+
+// momentum_kernel's shape with a second state vector
+template <typename G>
+__global__ void __launch_bounds__(MT)
+adamw_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m,
+             float* __restrict__ v, size_t n, const double* __restrict__ lr,
+             const AdamRecord* __restrict__ rec, float b1, float o1, float b2, float o2,
+             float eps, float wd, const DecayRanges R, float gscale,
+             const float* __restrict__ gate) {
+  // gate 0 skips the update: return before any access
+  if (gate && *gate == 0.f) return;
+  const float l = (float)(*lr);
+  const float lc = l * rec->c1, c2 = rec->c2;
+  const float lw = l * wd;
+  const size_t n4 = n / 4;
+  const int tid = threadIdx.x;
+  for (size_t c0 = blockIdx.x * (size_t)MT; c0 < n4; c0 += (size_t)gridDim.x * MT) {
+    const size_t i = c0 + tid;
+    const bool live = i < n4;
+    f32x4 pv, mv, vv;
+    decltype(grad4_raw(g, 0)) gv;
+    if (live) {
+      pv = ((const f32x4*)p)[i];
+      mv = ((const f32x4*)m)[i];
+      vv = ((const f32x4*)v)[i];
+      gv = grad4_raw(g, i);
+    }
+    const f32x4 w = chunk_mask(R, c0, tid, lw);
+    if (live) {
+      const f32x4 gf = grad4_f32(gv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], mj = mv[j], vj = vv[j];
+        adamw_update(pj, mj, vj, gf[j], w[j], lc, b1, o1, b2, o2, c2, eps, gscale);
+        pv[j] = pj, mv[j] = mj, vv[j] = vj;
+      }
+      ((f32x4*)m)[i] = mv;
+      ((f32x4*)v)[i] = vv;
+      ((f32x4*)p)[i] = pv;
+    }
+  }
+  // the n % 4 tail: at most three elements, one lane each
+  const size_t i = n4 * 4 + tid;
+  if (blockIdx.x == 0 && i < n) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_update(pi, mi, vi, grad_at(g, i), tail_mask(R, i, lw), lc, b1, o1, b2, o2, c2,
+                 eps, gscale);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+  }
+}
+
 }  // namespace
 
-extern "C" {
-
-hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const double* lr, float mu,
-                       int nesterov, float wd, const long long* ranges, int n_ranges,
-                       float gscale, const float* gate, const void* g16, hipStream_t s) {
-  if (n_ranges < 0 || n_ranges > MAX_RANGES || (n_ranges && !ranges))
-    return hipErrorInvalidValue;
-  DecayRanges R;
+// the host table {begin, end} x n_ranges -> R, or false: more than MAX_RANGES rows, a count
+// without a table, rows unsorted / overlapping / empty, a begin off RANGE_ALIGN, an end past n
+// or at 2^32 - 1 and above
+static bool decay_ranges(const long long* ranges, int n_ranges, size_t n, DecayRanges& R) {
+  if (n_ranges < 0 || n_ranges > MAX_RANGES || (n_ranges && !ranges)) return false;
   long long prev = 0;
   for (int q = 0; q < MAX_RANGES; ++q) {
     R.b[q] = R.e[q] = NO_RANGE;
@@ -137,25 +256,79 @@ hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const doubl
     const long long b = ranges[2 * q], e = ranges[2 * q + 1];
     if (b < prev || b % RANGE_ALIGN != 0 || e <= b || (unsigned long long)e > n ||
         e >= (long long)NO_RANGE)
-      return hipErrorInvalidValue;
+      return false;
     R.b[q] = (unsigned)b;
     R.e[q] = (unsigned)e;
     prev = e;
   }
+  return true;
+}
+
+// one pass per workgroup up to MAX_BLOCKS, at least one workgroup (the tail)
+static unsigned grid_blocks(size_t n) {
+  size_t blocks = (n / 4 + MT - 1) / MT;
+  if (blocks > MAX_BLOCKS) blocks = MAX_BLOCKS;
+  return blocks < 1 ? 1u : (unsigned)blocks;
+}
+
+extern "C" {
+
+hipError_t dg_momentum(float* p, const float* g, float* v, size_t n, const double* lr, float mu,
+                       int nesterov, float wd, const long long* ranges, int n_ranges,
+                       float gscale, const float* gate, const void* g16, hipStream_t s) {
+  DecayRanges R;
+  if (!decay_ranges(ranges, n_ranges, n, R)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!p || !v || !lr || !(g || g16)) return hipErrorInvalidValue;
   // the 16-byte (bf16: 8-byte) vector accesses
   if ((((uintptr_t)p | (uintptr_t)v | (uintptr_t)g) & 15) || ((uintptr_t)g16 & 7))
     return hipErrorInvalidValue;
-  size_t blocks = (n / 4 + MT - 1) / MT;
-  if (blocks > MAX_BLOCKS) blocks = MAX_BLOCKS;
-  if (blocks < 1) blocks = 1;
+  const unsigned blocks = grid_blocks(n);
   if (g16)
-    hipLaunchKernelGGL(momentum_kernel<bf16_t>, dim3((unsigned)blocks), dim3(MT), 0, s, p,
+    hipLaunchKernelGGL(momentum_kernel<bf16_t>, dim3(blocks), dim3(MT), 0, s, p,
                        (const bf16_t*)g16, v, n, lr, mu, nesterov, wd, R, gscale, gate);
   else
-    hipLaunchKernelGGL(momentum_kernel<float>, dim3((unsigned)blocks), dim3(MT), 0, s, p, g, v,
+    hipLaunchKernelGGL(momentum_kernel<float>, dim3(blocks), dim3(MT), 0, s, p, g, v,
                        n, lr, mu, nesterov, wd, R, gscale, gate);
+  return hipGetLastError();
+}
+
+hipError_t dg_adamw_tick(void* rec, float beta1, float beta2, const float* gate,
+                         hipStream_t s) {
+  // (written so that a NaN is refused too)
+  if (!rec || ((uintptr_t)rec & 7) || !(beta1 >= 0.f && beta1 < 1.f) ||
+      !(beta2 >= 0.f && beta2 < 1.f))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(adamw_tick, dim3(1), dim3(64), 0, s, (AdamRecord*)rec, beta1, beta2, gate);
+  return hipGetLastError();
+}
+
+hipError_t dg_adamw(float* p, const float* g, float* m, float* v, size_t n, const double* lr,
+                    void* rec, float beta1, float beta2, float eps, float wd,
+                    const long long* ranges, int n_ranges, float gscale, const float* gate,
+                    const void* g16, hipStream_t s) {
+  DecayRanges R;
+  if (!decay_ranges(ranges, n_ranges, n, R)) return hipErrorInvalidValue;
+  // (written so that a NaN is refused too)
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!p || !m || !v || !lr || !rec || !(g || g16)) return hipErrorInvalidValue;
+  // the 16-byte (bf16: 8-byte) vector accesses; the record's int64
+  if ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) ||
+      ((uintptr_t)g16 & 7) || ((uintptr_t)rec & 7))
+    return hipErrorInvalidValue;
+  const AdamRecord* r = (const AdamRecord*)rec;
+  if (hipError_t e = dg_adamw_tick(rec, beta1, beta2, gate, s)) return e;
+  const unsigned blocks = grid_blocks(n);
+  const float o1 = 1.f - beta1, o2 = 1.f - beta2;
+  if (g16)
+    hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(blocks), dim3(MT), 0, s, p,
+                       (const bf16_t*)g16, m, v, n, lr, r, beta1, o1, beta2, o2, eps, wd, R,
+                       gscale, gate);
+  else
+    hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(MT), 0, s, p, g, m, v, n, lr, r,
+                       beta1, o1, beta2, o2, eps, wd, R, gscale, gate);
   return hipGetLastError();
 }
 

@@ -2,11 +2,13 @@
 
 Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
 ``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module),
-``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise) and
+``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise),
+``deep_go_amd/_native/_dgadam<EXT>`` (the AdamW optimizer's kernels: the same optim.hip behind
+bindings of its own) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|cpu|comm]
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -118,6 +120,13 @@ def build_opt(force: bool = False) -> Path:
     return _build_small("opt", "optim.hip", "opt_bindings.cpp", force)
 
 
+def build_adam(force: bool = False) -> Path:
+    """_dgadam: AdamW (optim.hip, where it shares the decay ranges and gradient loads with
+    momentum, + adam_bindings.cpp).  A module of its own: the public names of _dgopt are
+    pinned by its tests."""
+    return _build_small("adam", "optim.hip", "adam_bindings.cpp", force)
+
+
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
     BUILD.mkdir(exist_ok=True)
     OUT.mkdir(exist_ok=True)
@@ -172,13 +181,14 @@ def build_all(force: bool = False) -> None:
     build_hip(force)
     build_aug(force)
     build_opt(force)
+    build_adam(force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "opt", "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -190,6 +200,8 @@ def main(argv=None):
         print(build_aug(a.force))
     if a.only in (None, "opt") and not a.sanitize:
         print(build_opt(a.force))
+    if a.only in (None, "adam") and not a.sanitize:
+        print(build_adam(a.force))
     if a.only in (None, "comm") and not a.sanitize:
         print(build_comm(a.force))
 

@@ -11,6 +11,10 @@ Parity notes (reference = Torch7 ``vipmath/deep-go``):
   experiments.  Here the layer schedule is derived, never mutated.
 * Unknown override keys are rejected (the reference silently ignored the typo
   ``validation_size`` in ``localtest.lua:8``).
+* ``optimizer`` has two additions to the reference's sgd | rmsprop: ``momentum`` (fields
+  ``momentum``, ``nesterov``, ``weight_decay``) and ``adamw`` (``adam_beta1``, ``adam_beta2``,
+  ``adam_eps``, ``weight_decay``).  ``override`` checks their ranges and rejects a field set
+  without the optimizer it belongs to; checkpoints from before a field existed load its default.
 """
 from __future__ import annotations
 
@@ -55,12 +59,19 @@ class ExperimentConfig:
     synthetic: bool = False        # synthetic boards instead of the on-disk dataset
     head_relu: bool = True         # reference applies ReLU to the head (parity)
     # sgd | rmsprop (the reference's misnamed AdagradOptimizer) | momentum (SGD with momentum,
-    # train/optim.py Momentum: the three fields below; they are rejected with sgd | rmsprop)
+    # train/optim.py Momentum: momentum, nesterov, weight_decay) | adamw (Adam with decoupled
+    # weight decay, train/optim.py AdamW: adam_beta1, adam_beta2, adam_eps, weight_decay; with
+    # weight_decay=0 it is Adam).  A field set without its optimizer is rejected, not ignored
     optimizer: str = "sgd"
     rmsprop_decay: float = 0.9
     momentum: float = 0.9          # velocity decay mu, in [0, 1)
     nesterov: bool = False         # step along gw + mu v instead of v
-    weight_decay: float = 0.0      # L2 coefficient on the conv weights (never on the biases)
+    # on the conv weights only (never on the biases): momentum's L2 coefficient (added to the
+    # gradient), adamw's decoupled decay (p *= 1 - rate * weight_decay)
+    weight_decay: float = 0.0
+    adam_beta1: float = 0.9        # first-moment decay, in [0, 1)
+    adam_beta2: float = 0.999      # second-moment decay, in [0, 1)
+    adam_eps: float = 1e-8         # added to the root of the second moment, > 0
     bucket_mb: float = 6.0         # DP gradient bucket size (12x128: head + hidden layers | layer 0)
     # DP all-reduce dtype: fp32 (the reference's DataParallelTable reduces fp32 gradients,
     # experiments.lua:155-168) | bf16 (opt-in: the wire twin every gradient pass 2 writes; half
@@ -180,7 +191,7 @@ def _coerce(name: str, value: Any, current: Any) -> Any:
 
 
 _CHOICES = {"nan_policy": ("guard", "skip", "raise"), "comm": ("auto", "native", "torch"),
-            "optimizer": ("sgd", "rmsprop", "momentum"), "grad_dtype": ("fp32", "bf16"),
+            "optimizer": ("sgd", "rmsprop", "momentum", "adamw"), "grad_dtype": ("fp32", "bf16"),
             "sampling": ("game", "position"), "augment": ("none", "d4")}
 
 
@@ -198,10 +209,22 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
         raise ValueError(f"momentum={new.momentum!r}: expected a value in [0, 1)")
     if new.weight_decay < 0.0:
         raise ValueError(f"weight_decay={new.weight_decay!r}: expected a value >= 0")
-    if new.optimizer != "momentum" and (new.nesterov or new.weight_decay != 0.0):
-        # (those two update paths have no such terms: do not ignore the setting silently)
-        raise ValueError(f"nesterov / weight_decay need optimizer=momentum, "
+    for k in ("adam_beta1", "adam_beta2"):
+        if not 0.0 <= getattr(new, k) < 1.0:
+            raise ValueError(f"{k}={getattr(new, k)!r}: expected a value in [0, 1)")
+    if not new.adam_eps > 0.0:
+        raise ValueError(f"adam_eps={new.adam_eps!r}: expected a value > 0")
+    # (the other update paths have no such terms: do not ignore a setting silently)
+    if new.optimizer != "momentum" and new.nesterov:
+        raise ValueError(f"nesterov needs optimizer=momentum, not optimizer={new.optimizer!r}")
+    if new.optimizer not in ("momentum", "adamw") and new.weight_decay != 0.0:
+        raise ValueError(f"weight_decay needs optimizer=momentum or adamw, "
                          f"not optimizer={new.optimizer!r}")
+    if new.optimizer != "adamw":
+        base = ExperimentConfig()
+        for k in ("adam_beta1", "adam_beta2", "adam_eps"):
+            if getattr(new, k) != getattr(base, k):
+                raise ValueError(f"{k} needs optimizer=adamw, not optimizer={new.optimizer!r}")
     return new
 
 

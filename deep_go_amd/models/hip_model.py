@@ -30,7 +30,7 @@ import torch
 from ..config import NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import hip, opt, stream_handle
+from ..ops.native import adam, hip, opt, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -237,6 +237,23 @@ class HipGoNet:
                                self.vel.data_ptr(), self.params.numel(), self.lr.data_ptr(),
                                0.0, 0, 0.0, self._wd_ranges.ctypes.data, len(self._wd_ranges),
                                1.0, torch.zeros(1, device=dev).data_ptr(), stream_handle())
+        # optimizer=adamw: the two moments, the 16-byte record {int64 t; float c1; float c2}
+        # of applied steps and their bias corrections (two int64: the second holds c1, c2),
+        # and the kernels' module (_dgadam: optim.hip)
+        self.adam_m = self.adam_v = self.adam_t = None
+        if cfg.optimizer == "adamw":
+            self.adam_m = torch.zeros_like(self.params)
+            self.adam_v = torch.zeros_like(self.params)
+            self.adam_t = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._opt = adam()
+            self._wd_ranges = np.ascontiguousarray(
+                np.array(self.layout.weight_ranges(), dtype=np.int64))
+            # both launches behind a closed gate (they return at once and t stays 0): the
+            # module's code object is loaded here, not inside the capture of a step graph
+            self._adamw(self._opt.adamw, self.grads.data_ptr(), 1.0,
+                        torch.zeros(1, device=dev).data_ptr(), stream_handle())
+        # the optimizers whose update is a launch of their own, not part of grad_update
+        self._own_update = self.vel is not None or self.adam_m is not None
         # non-finite loss guard (cfg.nan_policy == "skip"): device gate read by the optimizer
         self.gate = torch.ones(1, dtype=torch.float32, device=dev)
         self._gate_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # finite_gate1
@@ -1412,9 +1429,9 @@ class HipGoNet:
         needs the reduced gradient; the bf16 wire twin is a DP format), no gradient hooks, and
         every layer's slabs / partials in buffers of their own: one grouped weight-gradient
         launch, plus at most the first layer's own chain.  DG_FUSED_UPDATE=0: never (and the
-        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum: never (its
-        update is a launch of its own, not part of grad_update)."""
-        if not self.knobs.FUSED_UPDATE or self.vel is not None:
+        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum | adamw: never
+        (their update is a launch of its own, not part of grad_update)."""
+        if not self.knobs.FUSED_UPDATE or self._own_update:
             return False
         if self.global_batch != self.B or self.grads16 is not None or self.grad_hooks:
             return False
@@ -1484,7 +1501,8 @@ class HipGoNet:
         """The update: [finite gate] -> [fp8 scale update] -> ONE fused launch (grad_update:
         the gradient's pass 2 when the step deferred it, SGD / RMSProp on every parameter,
         the operand copies the next step reads, LR decay).  DG_FUSED_UPDATE=0: the separate
-        SGD / RMSProp and weight-refresh launches."""
+        SGD / RMSProp and weight-refresh launches.  optimizer=momentum | adamw: their own
+        launch(es) in the place of the SGD launch, then the weight refresh and LR decay."""
         s = stream_handle()
         n = self.layout.numel
         gate = self.gate.data_ptr() if self.cfg.nan_policy != "raise" else 0
@@ -1506,8 +1524,11 @@ class HipGoNet:
         self._gate_issued = False
         if not (slabs and self._early_issued):
             self._fp8_update(s)
-        if not self.knobs.FUSED_UPDATE or self.vel is not None:
-            if self.vel is not None:
+        if not self.knobs.FUSED_UPDATE or self._own_update:
+            if self.adam_m is not None:
+                self._adamw(self._opt.adamw_bf16 if w16 else self._opt.adamw, g, grad_scale,
+                            gate, s)
+            elif self.vel is not None:
                 r = self._wd_ranges
                 (self._opt.momentum_bf16 if w16 else self._opt.momentum)(
                     self.params.data_ptr(), g, self.vel.data_ptr(), n, self.lr.data_ptr(),
@@ -1535,6 +1556,22 @@ class HipGoNet:
             plain = (0, 0)
         self._early_issued = False
         self._gu_launch(t, plain, grad_scale, gate, 1, s)
+
+    def _adamw(self, fn, g, grad_scale, gate, s):
+        """optimizer=adamw's two launches (the count's, then the update): optim.hip."""
+        r, c = self._wd_ranges, self.cfg
+        fn(self.params.data_ptr(), g, self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+           self.layout.numel, self.lr.data_ptr(), self.adam_t.data_ptr(), float(c.adam_beta1),
+           float(c.adam_beta2), float(c.adam_eps), float(c.weight_decay), r.ctypes.data, len(r),
+           grad_scale, gate, s)
+
+    def adam_steps(self) -> int:
+        """optimizer=adamw: the steps applied so far (skipped ones do not count).  Syncs."""
+        return int(self.adam_t[0].item())
+
+    def set_adam_steps(self, t: int):
+        self.adam_t.zero_()            # (c1, c2 are rewritten before every use)
+        self.adam_t[0] = int(t)
 
     def _gu_launch(self, t, plain, grad_scale, gate, final, s):
         w16 = self.grads16 is not None

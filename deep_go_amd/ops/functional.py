@@ -425,6 +425,38 @@ def momentum_(p: torch.Tensor, g: torch.Tensor, v: torch.Tensor, lr: torch.Tenso
        stream_handle())
 
 
+def adamw_record(t: int = 0, device="cuda") -> torch.Tensor:
+    """AdamW's 16-byte device record {int64 t; float c1; float c2} as two int64 with the count
+    of applied steps in the first; ``adamw_record_values`` reads one back."""
+    rec = torch.zeros(2, dtype=torch.int64, device=device)
+    rec[0] = int(t)
+    return rec
+
+
+def adamw_record_values(rec: torch.Tensor):
+    """-> (t, c1, c2) of a record: the int and the two fp32 values as Python floats."""
+    c = rec[1:].cpu().view(torch.float32)
+    return int(rec[0].item()), float(c[0]), float(c[1])
+
+
+def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: torch.Tensor,
+           rec: torch.Tensor, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+           wd: float = 0.0, ranges=(), gscale: float = 1.0, gate: torch.Tensor | None = None):
+    """One AdamW step in place on the device vectors p, m, v (fp32) from the gradient g (fp32,
+    or bf16: the wire twin) — optim.hip; ``lr`` the device double, ``rec`` the record of
+    ``adamw_record`` (its count advances when the step is applied), ``ranges`` the [begin, end)
+    pairs weight decay applies to, ``gate`` an optional device float (0 skips the step)."""
+    from .native import adam
+    n = p.numel()
+    assert m.numel() == n and v.numel() == n and g.numel() == n and lr.dtype == torch.float64
+    assert rec.dtype == torch.int64 and rec.numel() == 2
+    r = np.ascontiguousarray(np.array(list(ranges), dtype=np.int64).reshape(-1, 2))
+    fn = adam().adamw_bf16 if g.dtype == torch.bfloat16 else adam().adamw
+    fn(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr.data_ptr(), rec.data_ptr(),
+       float(beta1), float(beta2), float(eps), float(wd), r.ctypes.data if len(r) else 0, len(r),
+       float(gscale), _ptr(gate), stream_handle())
+
+
 def policy_ensemble(logp: torch.Tensor, stones: torch.Tensor | None = None,
                     extra_illegal: torch.Tensor | None = None,
                     labels: torch.Tensor | None = None, S: int = 8, K: int = 5,

@@ -2,7 +2,8 @@
 
 ``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
 (the batch-augmentation kernel), imported only when augmentation is asked for; ``opt()`` the
-``_dgopt`` module (the momentum optimizer's kernel), imported only for it.  On a machine
+``_dgopt`` module (the momentum optimizer's kernel), imported only for it; ``adam()`` the
+``_dgadam`` module (the AdamW optimizer's kernels), likewise.  On a machine
 with a GPU a missing or stale extension is a hard error — there is deliberately no silent
 PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
 SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
@@ -36,7 +37,8 @@ def _load(name: str):
         if os.environ.get("DG_AUTOBUILD", "0") == "1":
             from .. import _build
             {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
-             "_dgopt": _build.build_opt, "_dgcomm": _build.build_comm}.get(
+             "_dgopt": _build.build_opt, "_dgadam": _build.build_adam,
+             "_dgcomm": _build.build_comm}.get(
                 name, _build.build_cpu)()
             mod = importlib.import_module(name)
         else:
@@ -59,6 +61,11 @@ def aug():
 def opt():
     """_dgopt: SGD with momentum / Nesterov / weight decay (csrc/kernels/optim.hip)."""
     return _load("_dgopt")
+
+
+def adam():
+    """_dgadam: AdamW, Adam with decoupled weight decay (csrc/kernels/optim.hip)."""
+    return _load("_dgadam")
 
 
 def cpu():

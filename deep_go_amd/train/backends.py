@@ -3,7 +3,7 @@
 Both expose the same small surface used by the training loop:
   set_batch(planes uint8 [B,9,19,19], player, rank, labels)   (host numpy or tensors)
   forward_backward()         loss/argmax of the batch + gradients (global-batch mean)
-  optimizer_step()           SGD/RMSProp/Momentum + per-step LR decay
+  optimizer_step()           SGD/RMSProp/Momentum/AdamW + per-step LR decay
   evaluate(n)                forward only on the first n boards of the current batch
   loss_sum() / correct()     of the last forward (host floats; synchronising)
   params / rate / state_dict / load_state_dict
@@ -33,7 +33,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, Momentum, RMSProp
+from .optim import SGD, AdamW, Momentum, RMSProp
 
 
 def _np(x, dtype):
@@ -71,6 +71,10 @@ class CPUBackend:
             self.opt = Momentum(cfg.rate, cfg.rateDecay, cfg.momentum, cfg.nesterov,
                                 cfg.weight_decay, self.layout.numel,
                                 self.layout.weight_ranges())
+        elif cfg.optimizer == "adamw":
+            self.opt = AdamW(cfg.rate, cfg.rateDecay, cfg.adam_beta1, cfg.adam_beta2,
+                             cfg.adam_eps, cfg.weight_decay, self.layout.numel,
+                             self.layout.weight_ranges())
         else:
             self.opt = SGD(cfg.rate, cfg.rateDecay)
         self._x = None
@@ -134,6 +138,7 @@ class CPUBackend:
                 np.isfinite(self._loss_sum) if self.world == 1
                 else bool(torch.isfinite(self.params.grad).all())):
             self.nan_skipped += 1
+            # (nothing of the optimizer's state moves: AdamW's count of applied steps neither)
             self.opt.rate = self.opt.rate * (1.0 - getattr(self.opt, "rate_decay", 0.0))
             return
         with torch.no_grad():
@@ -303,6 +308,11 @@ class HIPBackend:
             d["optimizer"]["ms"] = self.net.ms.detach().cpu()
         if self.net.vel is not None:
             d["optimizer"]["vel"] = self.net.vel.detach().cpu()
+        if self.net.adam_m is not None:
+            d["optimizer"]["adam_m"] = self.net.adam_m.detach().cpu()
+            d["optimizer"]["adam_v"] = self.net.adam_v.detach().cpu()
+            # (an integer: it travels in the checkpoint's metadata, not as a float tensor)
+            d["optimizer"]["adam_t"] = self.net.adam_steps()
         return d
 
     def close(self):
@@ -322,3 +332,10 @@ class HIPBackend:
                 self.net.vel.copy_(o["vel"].to(self.net.vel.device))
             else:
                 self.net.vel.zero_()
+        if self.net.adam_m is not None:
+            # (a checkpoint without moments: zero moments, no applied step)
+            has = "adam_m" in o and "adam_v" in o
+            for name in ("adam_m", "adam_v"):
+                t = getattr(self.net, name)
+                t.copy_(o[name].to(t.device)) if has else t.zero_()
+            self.net.set_adam_steps(int(o.get("adam_t", 0)) if has else 0)

@@ -1,6 +1,6 @@
 """Optimizers over the flat parameter vector (CPU path; the GPU path runs the same math in
-``sgd_kernel`` / ``rmsprop_kernel``, csrc/kernels/elementwise.hip, and ``momentum_kernel``,
-csrc/kernels/optim.hip).
+``sgd_kernel`` / ``rmsprop_kernel``, csrc/kernels/elementwise.hip, and ``momentum_kernel`` /
+``adamw_kernel``, csrc/kernels/optim.hip).
 
 * ``SGD`` (optimizer.lua:16-27): theta -= rate * g, then rate *= (1 - decay) — so after t
   steps rate_t = rate_0 * (1 - decay)^t.  The rate is a Python float (double), as in Lua.
@@ -12,6 +12,15 @@ csrc/kernels/optim.hip).
   gw = g elsewhere: v = momentum * v + gw (v starts at 0); theta -= rate * (gw + momentum * v
   if nesterov else v); then rate *= (1 - decay) as SGD.  This is torch.optim.SGD(momentum,
   dampening=0, nesterov, weight_decay) with the rate outside the velocity.
+* ``AdamW`` (an addition): Adam with decoupled weight decay on the conv weights only.  With the
+  moments m, v (0 at the start) and t, the count of APPLIED steps (0 at the start): t += 1;
+  c1 = 1 / (1 - beta1^t), c2 = 1 / sqrt(1 - beta2^t) (in double, then fp32); m = beta1 m +
+  (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; theta *= 1 - rate * weight_decay on the decayed
+  elements; theta -= (rate c1) m / (sqrt(v) c2 + eps); then rate *= (1 - decay) as SGD.  This is
+  torch.optim.AdamW(betas, eps, weight_decay, amsgrad=False); with weight_decay = 0 it is Adam.
+  A skipped step (a non-finite loss or gradient) is no call of ``step``: m, v and t stay, only
+  the rate decays, so t falls behind the trainer's iteration count.  beta1, beta2, eps are
+  taken as their fp32 values, as the kernel receives them.
 """
 from __future__ import annotations
 
@@ -86,3 +95,46 @@ class Momentum:
         self.rate_decay = float(d["rate_decay"])
         # (a checkpoint of another optimizer has no velocity: start from rest)
         self.vel = d["vel"].float().clone() if "vel" in d else torch.zeros_like(self.vel)
+
+
+class AdamW:
+    def __init__(self, rate: float, rate_decay: float, beta1: float, beta2: float, eps: float,
+                 weight_decay: float, numel: int, decay_ranges=()):
+        self.rate = float(rate)
+        self.rate_decay = float(rate_decay)
+        f32 = lambda x: torch.tensor(float(x), dtype=torch.float32).item()
+        self.beta1, self.beta2, self.eps = f32(beta1), f32(beta2), f32(eps)
+        self.m = torch.zeros(numel, dtype=torch.float32)
+        self.v = torch.zeros(numel, dtype=torch.float32)
+        self.t = 0                     # applied steps: what the bias corrections count
+        # weight_decay on the elements of decay_ranges ([begin, end) pairs), 0 elsewhere
+        self.wd = torch.zeros(numel, dtype=torch.float32)
+        for b, e in decay_ranges:
+            self.wd[b:e] = float(weight_decay)
+
+    @torch.no_grad()
+    def step(self, params: torch.Tensor, grads: torch.Tensor):
+        self.t += 1
+        f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+        c1 = f32(1.0 / (1.0 - self.beta1 ** self.t))
+        c2 = f32(1.0 / (1.0 - self.beta2 ** self.t) ** 0.5)
+        rate = f32(self.rate)
+        # (1 - beta is exact in fp32 arithmetic and in double alike)
+        self.m.mul_(self.beta1).add_(grads, alpha=1.0 - self.beta1)
+        self.v.mul_(self.beta2).add_((grads * (1.0 - self.beta2)).mul_(grads))
+        params.mul_(1.0 - rate * self.wd)
+        params.sub_((self.m * (rate * c1)).div_(self.v.sqrt().mul_(c2).add_(self.eps)))
+        self.rate = self.rate * (1.0 - self.rate_decay)
+
+    def state_dict(self):
+        return {"kind": "adamw", "rate": self.rate, "rate_decay": self.rate_decay,
+                "adam_m": self.m, "adam_v": self.v, "adam_t": int(self.t)}
+
+    def load_state_dict(self, d):
+        self.rate = float(d["rate"])
+        self.rate_decay = float(d["rate_decay"])
+        # (a checkpoint of another optimizer has no moments: start from zero, t = 0)
+        has = "adam_m" in d and "adam_v" in d
+        self.m = d["adam_m"].float().clone() if has else torch.zeros_like(self.m)
+        self.v = d["adam_v"].float().clone() if has else torch.zeros_like(self.v)
+        self.t = int(d.get("adam_t", 0)) if has else 0

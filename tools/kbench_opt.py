@@ -1,18 +1,21 @@
-"""optimizer=momentum (csrc/kernels/optim.hip, module _dgopt), measured.
+"""optimizer=momentum | adamw (csrc/kernels/optim.hip, modules _dgopt and _dgadam), measured.
 
-  kernel  momentum alone at the flat sizes of 12x128 and 12x256 with the model's own decay
-          ranges: device events around R back-to-back launches, beside the sgd and rmsprop
-          kernels of _dghip on the same vectors, five timings each in turn (so rmsprop's own
-          spread is on record), with the bytes each moves per element (sgd 12: p read and
-          written, g read; rmsprop and momentum 20: the state vector as well) and the
-          bandwidth that implies.  Gradients are zero and the rate tiny, so the vectors stay
-          finite over thousands of launches.
+  kernel  momentum and adamw alone at the flat sizes of 12x128 and 12x256 with the model's own
+          decay ranges: device events around R back-to-back launches, beside the sgd and
+          rmsprop kernels of _dghip on the same vectors, five timings each in turn (so
+          rmsprop's and momentum's own spread is on record), with the bytes each moves per
+          element (sgd 12: p read and written, g read; rmsprop and momentum 20: the state
+          vector as well; adamw 28: two state vectors) and the bandwidth that implies.  adamw
+          is timed as the trainer issues it, its one-wave count launch (adamw_tick) included;
+          that launch is also timed alone.  adamw's yardstick at each size is 1.4 x momentum's
+          median (28 / 20 bytes) + the tick's median + momentum's spread.  Gradients are zero
+          and the rate tiny, so the vectors stay finite over thousands of launches.
   step    the trainer's step through HIPBackend on the packed fixture (12x128 bf16, batch 256,
           input prefetch on): load_next + train_step, K steps per window ending in a device
           synchronise, windows of three variants alternating on one device: sgd (the fused,
           deferred update), sgd with DG_FUSED_UPDATE=0 (the separate launches momentum also
-          uses) and momentum.  A fourth backend, a second copy of sgd, is built and timed
-          between sgd and the unfused one (see the comment in step()).
+          uses), momentum and adamw.  A further backend, a second copy of sgd, is built and
+          timed between sgd and the unfused one (see the comment in step()).
 
 Usage: python tools/kbench_opt.py kernel [R] | step [K] [ROUNDS]
 -> one JSON line per mode.  bench.py is the headline benchmark; this tool only covers what the
@@ -46,10 +49,10 @@ def _events(fn, R):
 def kernel(R=2000):
     from deep_go_amd.config import ExperimentConfig
     from deep_go_amd.models.gocnn import ParamLayout, init_params
-    from deep_go_amd.ops.native import hip, opt, stream_handle
-    h, o, s = hip(), opt(), stream_handle()
+    from deep_go_amd.ops.native import adam, hip, opt, stream_handle
+    h, o, a, s = hip(), opt(), adam(), stream_handle()
     out = {"mode": "kernel", "launches": R, "unit": "us per launch",
-           "bytes_per_element": {"sgd": 12, "rmsprop": 20, "momentum": 20}}
+           "bytes_per_element": {"sgd": 12, "rmsprop": 20, "momentum": 20, "adamw": 28}}
     for ch in (128, 256):
         lay = ParamLayout(ExperimentConfig(numLayers=12, channelSize=ch))
         n = lay.numel
@@ -57,6 +60,8 @@ def kernel(R=2000):
         g = torch.zeros(n, device="cuda")
         ms = torch.ones(n, device="cuda")
         v = torch.zeros(n, device="cuda")
+        am, av = torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+        rec = torch.zeros(2, dtype=torch.int64, device="cuda")
         lr = torch.tensor([1e-6], dtype=torch.float64, device="cuda")
         gate = torch.ones(1, device="cuda")
         r = np.ascontiguousarray(np.array(lay.weight_ranges(), dtype=np.int64))
@@ -66,6 +71,9 @@ def kernel(R=2000):
             "rmsprop": lambda: h.rmsprop(P, G, ms.data_ptr(), n, LRP, 0.9, 1.0, GT, s),
             "momentum": lambda: o.momentum(P, G, v.data_ptr(), n, LRP, 0.9, 1, 1e-4,
                                            r.ctypes.data, len(r), 1.0, GT, s),
+            "adamw": lambda: a.adamw(P, G, am.data_ptr(), av.data_ptr(), n, LRP, rec.data_ptr(),
+                                     0.9, 0.999, 1e-8, 1e-4, r.ctypes.data, len(r), 1.0, GT, s),
+            "adamw_tick": lambda: a.adamw_tick(rec.data_ptr(), 0.9, 0.999, GT, s),
         }
         res = {"elements": n, **{k: [] for k in runs}}
         for _ in range(5):
@@ -74,11 +82,18 @@ def kernel(R=2000):
         for name in runs:
             med = statistics.median(res[name])
             res[name + "_median"] = med
-            res[name + "_GBps"] = round(out["bytes_per_element"][name] * n / med / 1e3, 1)
+            if name in out["bytes_per_element"]:
+                res[name + "_GBps"] = round(out["bytes_per_element"][name] * n / med / 1e3, 1)
         res["momentum_minus_rmsprop_median_us"] = round(
             res["momentum_median"] - res["rmsprop_median"], 3)
         res["rmsprop_spread_us"] = round(max(res["rmsprop"]) - min(res["rmsprop"]), 3)
+        res["momentum_spread_us"] = round(max(res["momentum"]) - min(res["momentum"]), 3)
+        res["adamw_yardstick_us"] = round(1.4 * res["momentum_median"] + res["adamw_tick_median"]
+                                          + res["momentum_spread_us"], 3)
+        res["adamw_minus_yardstick_us"] = round(
+            res["adamw_median"] - res["adamw_yardstick_us"], 3)
         assert torch.isfinite(p).all() and torch.isfinite(v).all()
+        assert torch.isfinite(am).all() and torch.isfinite(av).all()
         out[f"12x{ch}"] = res
     print(json.dumps(out), flush=True)
 
@@ -94,10 +109,12 @@ def step(K=300, rounds=6, B=256):
     # found.  A second copy of sgd takes that place and is reported under its own name, so
     # the three variants compared sit in places that have behaved alike)
     variants = {"sgd": ("sgd", None), "sgd_copy_before_unfused": ("sgd", None),
-                "sgd_unfused": ("sgd", "0"), "momentum": ("momentum", None)}
+                "sgd_unfused": ("sgd", "0"), "momentum": ("momentum", None),
+                "adamw": ("adamw", None)}
     runs = {}
     for name, (optimizer, fused) in variants.items():
-        kw = dict(momentum=0.9, nesterov=True, weight_decay=1e-4) if optimizer == "momentum" else {}
+        kw = {"momentum": dict(momentum=0.9, nesterov=True, weight_decay=1e-4),
+              "adamw": dict(weight_decay=1e-2)}.get(optimizer, {})
         cfg = get_preset("12x128-bf16", batchSize=B, synthetic=False, data_root=FIXTURE,
                          rate=1e-3, optimizer=optimizer, **kw)
         old = os.environ.pop("DG_FUSED_UPDATE", None)
@@ -143,6 +160,9 @@ def step(K=300, rounds=6, B=256):
     out["sgd_unfused_minus_sgd_median_us"] = round(
         out["sgd_unfused_median"] - out["sgd_median"], 2)
     out["momentum_minus_sgd_median_us"] = round(out["momentum_median"] - out["sgd_median"], 2)
+    out["adamw_minus_momentum_median_us"] = round(
+        out["adamw_median"] - out["momentum_median"], 2)
+    out["adamw_minus_sgd_median_us"] = round(out["adamw_median"] - out["sgd_median"], 2)
     for be, _ in runs.values():
         assert torch.isfinite(be.net.params).all()
         be.close()
