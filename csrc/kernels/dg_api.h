@@ -334,4 +334,25 @@ hipError_t dg_adamw(float* p, const float* g, float* m, float* v, size_t n, cons
                     const long long* ranges, int n_ranges, float gscale, const float* gate,
                     const void* g16, hipStream_t s);
 
+// ---------------------------------------------------------------- clip.hip (module _dgclip)
+// Global-norm gradient clipping over the flat gradient: norm = |gscale| sqrt(sum g^2); r =
+// max_norm / (norm + 1e-6); scale = r < 1 ? r : 1; g *= scale (the optimizer behind it still
+// applies gscale).  Two launches on s: up to dg_clip_partials() workgroups each write one fp32
+// partial of the sum of squares to part (part_n >= dg_clip_partials() floats), then every
+// workgroup sums the partials in double in one fixed order and scales its share.  No atomics:
+// the same input gives the same bits.  rec: the 16-byte device record {float norm; float scale;
+// int64 clipped} (8-byte aligned), clipped += 1 when scale < 1.  Exactly one of g (fp32,
+// 16-byte aligned: scaled in place, untouched when scale == 1; out must be null) and g16 (the
+// bf16 wire twin, 8-byte aligned: only read; out[i] = scale * float(g16[i]) is always written,
+// out fp32 and 16-byte aligned).  gate 0 leaves g, out, part and rec untouched.  max_norm > 0
+// and finite, gscale finite; n == 0 launches nothing.
+int dg_clip_partials();
+hipError_t dg_grad_clip(float* g, const void* g16, float* out, size_t n, float* part,
+                        int part_n, void* rec, float max_norm, float gscale, const float* gate,
+                        hipStream_t s);
+// the first launch alone: part[b] for b below min(ceil(floor(n / 4) / 256), dg_clip_partials()),
+// at least one; sum them for sum g^2
+hipError_t dg_grad_norm(const float* g, const void* g16, size_t n, float* part, int part_n,
+                        const float* gate, hipStream_t s);
+
 }  // extern "C"

@@ -4,11 +4,12 @@ Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
 ``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module),
 ``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise),
 ``deep_go_amd/_native/_dgadam<EXT>`` (the AdamW optimizer's kernels: the same optim.hip behind
-bindings of its own) and
+bindings of its own),
+``deep_go_amd/_native/_dgclip<EXT>`` (gradient clipping by the global norm: clip.hip) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|cpu|comm]
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|clip|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -127,6 +128,12 @@ def build_adam(force: bool = False) -> Path:
     return _build_small("adam", "optim.hip", "adam_bindings.cpp", force)
 
 
+def build_clip(force: bool = False) -> Path:
+    """_dgclip: global-norm gradient clipping (clip.hip + clip_bindings.cpp), imported only for
+    grad_clip > 0 and apart from the other modules, whose interfaces are recorded or pinned."""
+    return _build_small("clip", "clip.hip", "clip_bindings.cpp", force)
+
+
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
     BUILD.mkdir(exist_ok=True)
     OUT.mkdir(exist_ok=True)
@@ -182,13 +189,14 @@ def build_all(force: bool = False) -> None:
     build_aug(force)
     build_opt(force)
     build_adam(force)
+    build_clip(force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "clip", "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -202,6 +210,8 @@ def main(argv=None):
         print(build_opt(a.force))
     if a.only in (None, "adam") and not a.sanitize:
         print(build_adam(a.force))
+    if a.only in (None, "clip") and not a.sanitize:
+        print(build_clip(a.force))
     if a.only in (None, "comm") and not a.sanitize:
         print(build_comm(a.force))
 

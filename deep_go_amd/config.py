@@ -15,6 +15,10 @@ Parity notes (reference = Torch7 ``vipmath/deep-go``):
   ``momentum``, ``nesterov``, ``weight_decay``) and ``adamw`` (``adam_beta1``, ``adam_beta2``,
   ``adam_eps``, ``weight_decay``).  ``override`` checks their ranges and rejects a field set
   without the optimizer it belongs to; checkpoints from before a field existed load its default.
+* ``grad_clip`` (an addition; 0 = off) caps the gradient's global L2 norm before any of the four
+  optimizers reads it: with c = grad_clip, norm = |gscale| * ||g||_2, scale = min(1, c / (norm +
+  1e-6)), g *= scale — ``torch.nn.utils.clip_grad_norm_`` (train/optim.py clip_grad_).  Once per
+  APPLIED step: a skipped step clips nothing.  ``override`` refuses a negative or non-finite value.
 """
 from __future__ import annotations
 
@@ -72,6 +76,10 @@ class ExperimentConfig:
     adam_beta1: float = 0.9        # first-moment decay, in [0, 1)
     adam_beta2: float = 0.999      # second-moment decay, in [0, 1)
     adam_eps: float = 1e-8         # added to the root of the second moment, > 0
+    # the cap on the gradient's global L2 norm (0 = off; train/optim.py clip_grad_), valid with
+    # every optimizer.  On the GPU sgd | rmsprop then take their separate launches instead of
+    # the fused, deferred update
+    grad_clip: float = 0.0
     bucket_mb: float = 6.0         # DP gradient bucket size (12x128: head + hidden layers | layer 0)
     # DP all-reduce dtype: fp32 (the reference's DataParallelTable reduces fp32 gradients,
     # experiments.lua:155-168) | bf16 (opt-in: the wire twin every gradient pass 2 writes; half
@@ -214,6 +222,9 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
             raise ValueError(f"{k}={getattr(new, k)!r}: expected a value in [0, 1)")
     if not new.adam_eps > 0.0:
         raise ValueError(f"adam_eps={new.adam_eps!r}: expected a value > 0")
+    # (written so that a NaN is refused too)
+    if not 0.0 <= new.grad_clip < float("inf"):
+        raise ValueError(f"grad_clip={new.grad_clip!r}: expected a finite value >= 0 (0 = off)")
     # (the other update paths have no such terms: do not ignore a setting silently)
     if new.optimizer != "momentum" and new.nesterov:
         raise ValueError(f"nesterov needs optimizer=momentum, not optimizer={new.optimizer!r}")

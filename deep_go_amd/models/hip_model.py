@@ -30,7 +30,7 @@ import torch
 from ..config import NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import adam, hip, opt, stream_handle
+from ..ops.native import adam, clip, hip, opt, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -252,8 +252,22 @@ class HipGoNet:
             # module's code object is loaded here, not inside the capture of a step graph
             self._adamw(self._opt.adamw, self.grads.data_ptr(), 1.0,
                         torch.zeros(1, device=dev).data_ptr(), stream_handle())
-        # the optimizers whose update is a launch of their own, not part of grad_update
-        self._own_update = self.vel is not None or self.adam_m is not None
+        # grad_clip > 0: the partials of the gradient's sum of squares, the 16-byte record
+        # {float norm; float scale; int64 clipped} (two int64: the first holds norm, scale) and
+        # the kernels' module (_dgclip: clip.hip).  The clip scans the reduced gradient, so
+        # every optimizer then takes a launch of its own behind it
+        self.clip_part = self.clip_rec = self._clip = None
+        if cfg.grad_clip > 0:
+            self._clip = clip()
+            self.clip_part = torch.zeros(self._clip.clip_partials(), dtype=torch.float32,
+                                         device=dev)
+            self.clip_rec = torch.zeros(2, dtype=torch.int64, device=dev)
+            # both launches behind a closed gate (they return at once and the record stays
+            # zero): the module's code object is loaded here, not inside a graph capture
+            self._grad_clip(1.0, torch.zeros(1, device=dev).data_ptr(), stream_handle())
+        # the updates that are a launch of their own, not part of grad_update
+        self._own_update = (self.vel is not None or self.adam_m is not None
+                            or self._clip is not None)
         # non-finite loss guard (cfg.nan_policy == "skip"): device gate read by the optimizer
         self.gate = torch.ones(1, dtype=torch.float32, device=dev)
         self._gate_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # finite_gate1
@@ -1429,8 +1443,9 @@ class HipGoNet:
         needs the reduced gradient; the bf16 wire twin is a DP format), no gradient hooks, and
         every layer's slabs / partials in buffers of their own: one grouped weight-gradient
         launch, plus at most the first layer's own chain.  DG_FUSED_UPDATE=0: never (and the
-        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum | adamw: never
-        (their update is a launch of its own, not part of grad_update)."""
+        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum | adamw, or
+        grad_clip > 0 with any optimizer: never (their update is a launch of its own behind the
+        reduced gradient, not part of grad_update)."""
         if not self.knobs.FUSED_UPDATE or self._own_update:
             return False
         if self.global_batch != self.B or self.grads16 is not None or self.grad_hooks:
@@ -1502,7 +1517,9 @@ class HipGoNet:
         the gradient's pass 2 when the step deferred it, SGD / RMSProp on every parameter,
         the operand copies the next step reads, LR decay).  DG_FUSED_UPDATE=0: the separate
         SGD / RMSProp and weight-refresh launches.  optimizer=momentum | adamw: their own
-        launch(es) in the place of the SGD launch, then the weight refresh and LR decay."""
+        launch(es) in the place of the SGD launch, then the weight refresh and LR decay.
+        grad_clip > 0: the clip's two launches in front of the optimizer's, which is then a
+        separate launch for sgd | rmsprop too and reads the fp32 gradient."""
         s = stream_handle()
         n = self.layout.numel
         gate = self.gate.data_ptr() if self.cfg.nan_policy != "raise" else 0
@@ -1524,6 +1541,11 @@ class HipGoNet:
         self._gate_issued = False
         if not (slabs and self._early_issued):
             self._fp8_update(s)
+        if self._clip is not None:
+            # bf16 wire: the clip widens the scaled twin into self.grads (one bf16 rounding,
+            # the wire's); the optimizer reads that
+            self._grad_clip(grad_scale, gate, s)
+            w16, g = False, self.grads.data_ptr()
         if not self.knobs.FUSED_UPDATE or self._own_update:
             if self.adam_m is not None:
                 self._adamw(self._opt.adamw_bf16 if w16 else self._opt.adamw, g, grad_scale,
@@ -1564,6 +1586,23 @@ class HipGoNet:
            self.layout.numel, self.lr.data_ptr(), self.adam_t.data_ptr(), float(c.adam_beta1),
            float(c.adam_beta2), float(c.adam_eps), float(c.weight_decay), r.ctypes.data, len(r),
            grad_scale, gate, s)
+
+    def _grad_clip(self, grad_scale, gate, s):
+        """grad_clip's two launches (the partial sums of squares, then the scale): clip.hip."""
+        n, c = self.layout.numel, float(self.cfg.grad_clip)
+        part, rec = self.clip_part.data_ptr(), self.clip_rec.data_ptr()
+        if self.grads16 is not None:
+            self._clip.grad_clip_bf16(self.grads16.data_ptr(), self.grads.data_ptr(), n, part,
+                                      self.clip_part.numel(), rec, c, grad_scale, gate, s)
+        else:
+            self._clip.grad_clip(self.grads.data_ptr(), n, part, self.clip_part.numel(), rec, c,
+                                 grad_scale, gate, s)
+
+    def clip_stats(self):
+        """grad_clip > 0: (norm, scale) of the last applied step and the number of applied
+        steps that clipped so far, from the device record.  Syncs."""
+        norm, scale = self.clip_rec[0:1].view(torch.float32).tolist()
+        return norm, scale, int(self.clip_rec[1].item())
 
     def adam_steps(self) -> int:
         """optimizer=adamw: the steps applied so far (skipped ones do not count).  Syncs."""

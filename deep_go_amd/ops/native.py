@@ -3,7 +3,8 @@
 ``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
 (the batch-augmentation kernel), imported only when augmentation is asked for; ``opt()`` the
 ``_dgopt`` module (the momentum optimizer's kernel), imported only for it; ``adam()`` the
-``_dgadam`` module (the AdamW optimizer's kernels), likewise.  On a machine
+``_dgadam`` module (the AdamW optimizer's kernels), likewise; ``clip()`` the ``_dgclip`` module
+(gradient clipping by the global norm), imported only for ``grad_clip > 0``.  On a machine
 with a GPU a missing or stale extension is a hard error — there is deliberately no silent
 PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
 SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
@@ -38,6 +39,7 @@ def _load(name: str):
             from .. import _build
             {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
              "_dgopt": _build.build_opt, "_dgadam": _build.build_adam,
+             "_dgclip": _build.build_clip,
              "_dgcomm": _build.build_comm}.get(
                 name, _build.build_cpu)()
             mod = importlib.import_module(name)
@@ -66,6 +68,11 @@ def opt():
 def adam():
     """_dgadam: AdamW, Adam with decoupled weight decay (csrc/kernels/optim.hip)."""
     return _load("_dgadam")
+
+
+def clip():
+    """_dgclip: gradient clipping by the global L2 norm (csrc/kernels/clip.hip)."""
+    return _load("_dgclip")
 
 
 def cpu():

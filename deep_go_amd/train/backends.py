@@ -6,6 +6,8 @@ Both expose the same small surface used by the training loop:
   optimizer_step()           SGD/RMSProp/Momentum/AdamW + per-step LR decay
   evaluate(n)                forward only on the first n boards of the current batch
   loss_sum() / correct()     of the last forward (host floats; synchronising)
+  clip_stats()               grad_clip > 0: (grad_norm, clip_scale, clipped_steps) of the last
+                             applied step and of the run (synchronising)
   params / rate / state_dict / load_state_dict
 
 ``load_next(loader)`` feeds the next training batch; with ``cfg.augment == "d4"`` it moves every
@@ -33,7 +35,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, AdamW, Momentum, RMSProp
+from .optim import SGD, AdamW, Momentum, RMSProp, clip_grad_
 
 
 def _np(x, dtype):
@@ -86,6 +88,9 @@ class CPUBackend:
             ranges = [self.layout.layer_range(i) for i in range(len(self.layout.layers))]
             self.buckets = dp.make_buckets(ranges, int(bucket_mb * 2 ** 20))
         self.nan_skipped = 0
+        # grad_clip > 0: the last applied step's norm and scale, the applied steps that clipped
+        # (a statistic of the run: not part of a checkpoint)
+        self._clip = (0.0, 0.0, 0)
         self._last = "train"
         self._eval = (0.0, 0)
 
@@ -142,6 +147,9 @@ class CPUBackend:
             self.opt.rate = self.opt.rate * (1.0 - getattr(self.opt, "rate_decay", 0.0))
             return
         with torch.no_grad():
+            if self.cfg.grad_clip > 0:
+                norm, scale = clip_grad_(self.params.grad, self.cfg.grad_clip)
+                self._clip = (norm, scale, self._clip[2] + (scale < 1.0))
             self.opt.step(self.params, self.params.grad)
 
     @torch.no_grad()
@@ -168,6 +176,11 @@ class CPUBackend:
     def gradient_tagged(self) -> bool:
         """(HIP only: the gradient producers' range-check tag; the fp32 oracle has none)"""
         return False
+
+    def clip_stats(self):
+        """grad_clip > 0: (grad_norm, clip_scale) of the last applied step and the number of
+        applied steps that clipped so far."""
+        return self._clip
 
     def flat_params(self) -> torch.Tensor:
         return self.params.detach()
@@ -294,6 +307,11 @@ class HIPBackend:
             return False
         step, tag = self.net._stepflag.tolist()
         return tag == step + 1
+
+    def clip_stats(self):
+        """grad_clip > 0: (grad_norm, clip_scale) of the last applied step and the number of
+        applied steps that clipped so far, from the device record (syncs)."""
+        return self.net.clip_stats()
 
     def flat_params(self) -> torch.Tensor:
         return self.net.params.detach().cpu()

@@ -276,6 +276,11 @@ class Experiment:
                 if not fused:
                     with trace.range("optimizer"):
                         be.optimizer_step()
+                if cfg.grad_clip > 0 and step % cfg.log_interval == 0:
+                    # (after the update: the norm and scale this step's update used)
+                    gn, cs, nclip = be.clip_stats()
+                    self.metrics.record(kind="clip", step=step, grad_norm=gn, clip_scale=cs,
+                                        clipped_steps=nclip)
                 # (after the update: the device's skip counter then includes this step)
                 if skipguard is not None:
                     skipguard.step()

@@ -21,10 +21,37 @@
   A skipped step (a non-finite loss or gradient) is no call of ``step``: m, v and t stay, only
   the rate decays, so t falls behind the trainer's iteration count.  beta1, beta2, eps are
   taken as their fp32 values, as the kernel receives them.
+
+``clip_grad_`` (an addition; ``grad_clip`` > 0) runs before any of them, once per applied step:
+norm = |gscale| * sqrt(sum g^2), scale = min(1, c / (norm + 1e-6)), g *= scale, which is
+``torch.nn.utils.clip_grad_norm_(params, c)`` applied to g * gscale (the GPU path:
+csrc/kernels/clip.hip).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
+
+
+@torch.no_grad()
+def clip_grad_(grads: torch.Tensor, max_norm: float, gscale: float = 1.0):
+    """Scale the flat fp32 gradient in place so that |gscale| * ||grads||_2 <= max_norm;
+    returns (norm, scale) as the fp32 values the GPU record holds.  The sum of squares is
+    accumulated in float64 from the fp32 gradient; the norm is rounded to fp32, r = max_norm /
+    (norm + 1e-6) is formed in double from that fp32 norm (max_norm and gscale as their fp32
+    values, as the kernel receives them), and scale = fp32(r) if r < 1 else 1 is applied in
+    fp32.  An infinite norm gives scale 0, a NaN norm scale 1, as torch does."""
+    c, s = float(np.float32(max_norm)), abs(float(np.float32(gscale)))
+    g64 = grads.double()
+    # (the float64 sum does not overflow where the kernel's fp32 partials do; the norm's own
+    # rounding to fp32 may)
+    with np.errstate(over="ignore"):
+        norm = float(np.float32(s * float(torch.dot(g64, g64)) ** 0.5))
+    r = c / (norm + 1e-6)
+    scale = float(np.float32(r)) if r < 1.0 else 1.0
+    if scale != 1.0:
+        grads.mul_(scale)
+    return norm, scale
 
 
 class SGD:
