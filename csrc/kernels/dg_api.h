@@ -355,4 +355,16 @@ hipError_t dg_grad_clip(float* g, const void* g16, float* out, size_t n, float* 
 hipError_t dg_grad_norm(const float* g, const void* g16, size_t n, float* part, int part_n,
                         const float* gate, hipStream_t s);
 
+// ------------------------------------------------------------------ ema.hip (module _dgema)
+// An exponential moving average e of the flat parameter vector p, once per APPLIED step:
+// t += 1; d = min(decay, (1 + t) / (10 + t)) in double; omd = float(1 - d); e[i] = fmaf(omd,
+// p[i] - e[i], e[i]).  rec: the average's 16-byte device record {int64 t; float omd; float pad}
+// (8-byte aligned), t the count of applied steps.  Two launches on s: dg_ema_tick (one wave:
+// behind an open gate t += 1 and omd; nothing behind a closed one), then the average, which
+// only reads omd and p.  gate 0 leaves e and rec untouched.  p, e 16-byte aligned and not null,
+// decay in [0, 1); n == 0 launches nothing.
+hipError_t dg_ema_tick(void* rec, double decay, const float* gate, hipStream_t s);
+hipError_t dg_ema(const float* p, float* e, size_t n, void* rec, double decay, const float* gate,
+                  hipStream_t s);
+
 }  // extern "C"

@@ -4,14 +4,17 @@
             (localtest.lua / default-experiment.lua / notebook equivalents via presets)
   resume    CKPT --iters N [--reset-optimizer] [--id NAME] [key=value ...]
             (experiments/repeated.lua: -gpu/-num/-iters -> --device/--id/--iters)
-  eval      CKPT [--split test] [--n N] [--symmetries 8] [--top K]
+  eval      CKPT [--split test] [--n N] [--symmetries 8] [--top K] [--ema]
             (top-1 / NLL on a split; never done in the ref.  With --symmetries / --top also the
             symmetry-ensembled, legality-masked top-k accuracy and mean rank: deep_go_amd.predict)
   predict   CKPT GAME.sgf [--move N] [--top K] [--symmetries {1,8}] [--device auto|cpu|gpu] [--all]
+            [--ema]
             (where to play and with what probability: one JSON line per requested move)
   makedata  scatter SRC DST train=N validation=N test=N | transcribe SRC DST [--threads T] [--ko]
             | count ROOT SPLIT | pack ROOT SPLIT
-  export    CKPT OUT.t7        (reference Torch7 experiment table)
+  export    CKPT OUT.t7 [--ema] (reference Torch7 experiment table)
+            (--ema, here and for eval / predict: the checkpoint's moving average of the weights,
+            ema_decay > 0, in the place of its parameters; an error if it carries none)
   import    IN.t7 OUT.model
   plot      FILE... [--out PNG] (validation/training curves from checkpoints or JSONL; plot.lua)
   bench     [bench.py args]
@@ -92,7 +95,12 @@ def cmd_resume(args):
 
 def cmd_eval(args):
     from .train.experiment import Experiment
-    e = Experiment.load(args.checkpoint)
+    try:
+        e = Experiment.load(args.checkpoint, ema=args.ema)
+    except ValueError as err:
+        if not args.ema:
+            raise
+        raise SystemExit(f"eval --ema: {err}")
     if args.device == "cpu":
         e.cfg = e.cfg.replace(useCuda=False)
     extra = {}
@@ -102,6 +110,8 @@ def cmd_eval(args):
             extra = _eval_ensemble(e, args)
     finally:
         e.close()
+    if args.ema:
+        extra = {"ema": True, **extra}
     print(json.dumps({"split": args.split, "cost": cost, "accuracy": acc, **extra}))
     return 0
 
@@ -131,8 +141,13 @@ def _sgf_point(p: int):
 
 def cmd_predict(args):
     from .predict import Predictor, ko_mask, positions_from_sgf
-    p = Predictor.load(args.checkpoint, symmetries=args.symmetries, top=args.top,
-                       device=args.device, batch=64)
+    try:
+        p = Predictor.load(args.checkpoint, ema=args.ema, symmetries=args.symmetries,
+                           top=args.top, device=args.device, batch=64)
+    except ValueError as err:
+        if not args.ema:
+            raise
+        raise SystemExit(f"predict --ema: {err}")
     with open(args.sgf, newline="") as f:
         text = f.read()
     planes, player, rank, label, ko = positions_from_sgf(text, mark_ko=p.cfg.ko_plane)
@@ -177,6 +192,11 @@ def cmd_makedata(args):
 def cmd_export(args):
     from .utils import checkpoint as ck
     cfg, flat, state, opt = ck.load_checkpoint(args.checkpoint)
+    if args.ema:
+        try:
+            flat = ck.ema_params(args.checkpoint, flat, opt)
+        except ValueError as err:
+            raise SystemExit(f"export --ema: {err}")
     ck.export_t7(args.out, cfg, flat, state, float(opt.get("rate", cfg.rate)))
     print(args.out)
     return 0
@@ -234,6 +254,8 @@ def main(argv=None):
     e.add_argument("--symmetries", type=int, choices=[1, 8],
                    help="also report the symmetry-ensembled top-k accuracy / mean rank")
     e.add_argument("--top", type=int, help="k of topk_accuracy (default 5)")
+    e.add_argument("--ema", action="store_true",
+                   help="evaluate the checkpoint's moving average of the weights (ema_decay > 0)")
     e.set_defaults(fn=cmd_eval)
     q = sub.add_parser("predict")
     q.add_argument("checkpoint")
@@ -243,6 +265,8 @@ def main(argv=None):
     q.add_argument("--symmetries", type=int, choices=[1, 8], default=8)
     q.add_argument("--device", choices=["auto", "cpu", "gpu"], default="auto")
     q.add_argument("--all", action="store_true", help="every move of the game")
+    q.add_argument("--ema", action="store_true",
+                   help="predict with the checkpoint's moving average of the weights")
     q.set_defaults(fn=cmd_predict)
     m = sub.add_parser("makedata")
     m.add_argument("--threads", type=int, default=32)
@@ -254,6 +278,8 @@ def main(argv=None):
     x = sub.add_parser("export")
     x.add_argument("checkpoint")
     x.add_argument("out")
+    x.add_argument("--ema", action="store_true",
+                   help="export the checkpoint's moving average of the weights")
     x.set_defaults(fn=cmd_export)
     i = sub.add_parser("import")
     i.add_argument("t7")

@@ -19,6 +19,11 @@ Parity notes (reference = Torch7 ``vipmath/deep-go``):
   optimizers reads it: with c = grad_clip, norm = |gscale| * ||g||_2, scale = min(1, c / (norm +
   1e-6)), g *= scale — ``torch.nn.utils.clip_grad_norm_`` (train/optim.py clip_grad_).  Once per
   APPLIED step: a skipped step clips nothing.  ``override`` refuses a negative or non-finite value.
+* ``ema_decay`` (an addition; 0 = off) keeps an exponential moving average of the weights beside
+  them (train/optim.py WeightEMA): after every APPLIED step t += 1, d = min(ema_decay, (1 + t) /
+  (10 + t)), e += (1 - d) (p - e).  Training never reads it; validation also reports it, and
+  ``eval`` / ``predict`` / ``export`` ``--ema`` serve it.  ``override`` refuses a value outside
+  [0, 1) and a NaN.
 """
 from __future__ import annotations
 
@@ -80,6 +85,9 @@ class ExperimentConfig:
     # every optimizer.  On the GPU sgd | rmsprop then take their separate launches instead of
     # the fused, deferred update
     grad_clip: float = 0.0
+    # the decay of the exponential moving average of the weights (0 = off; train/optim.py
+    # WeightEMA), in [0, 1), valid with every optimizer; it changes nothing of the training itself
+    ema_decay: float = 0.0
     bucket_mb: float = 6.0         # DP gradient bucket size (12x128: head + hidden layers | layer 0)
     # DP all-reduce dtype: fp32 (the reference's DataParallelTable reduces fp32 gradients,
     # experiments.lua:155-168) | bf16 (opt-in: the wire twin every gradient pass 2 writes; half
@@ -225,6 +233,8 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
     # (written so that a NaN is refused too)
     if not 0.0 <= new.grad_clip < float("inf"):
         raise ValueError(f"grad_clip={new.grad_clip!r}: expected a finite value >= 0 (0 = off)")
+    if not 0.0 <= new.ema_decay < 1.0:
+        raise ValueError(f"ema_decay={new.ema_decay!r}: expected a value in [0, 1) (0 = off)")
     # (the other update paths have no such terms: do not ignore a setting silently)
     if new.optimizer != "momentum" and new.nesterov:
         raise ValueError(f"nesterov needs optimizer=momentum, not optimizer={new.optimizer!r}")

@@ -18,6 +18,7 @@ batch 256 needs < 1 GB of HBM, so nothing is ever re-allocated in the step.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
 from collections import namedtuple
@@ -30,7 +31,7 @@ import torch
 from ..config import NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import adam, clip, hip, opt, stream_handle
+from ..ops.native import adam, clip, ema, hip, opt, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -59,6 +60,9 @@ REFRESH_PARTS = 512   # weight_refresh workgroups per layer (elementwise.hip)
 RT_WEIGHT_COPIES = {1: "wf", 2: "wd", 10: "wf8", 16: "wf_frag", 17: "wd_frag",
                     18: "wf8_frag", 19: "wd8_frag"}
 RT_PBIAS_FRAG, RT_PBIAS = 9, 15
+# the master-weight inputs: absolute addresses into the flat parameter vector (weights,
+# per-channel bias, per-position bias)
+RT_MASTER = (0, 13, 14)
 # grad_update row (_gu_table; elementwise.hip dg_grad_update): the refresh row, then where
 # the layer's gradient comes from
 GU_SLAB, GU_BPART, GU_SPLITS = 20, 21, 22
@@ -268,6 +272,18 @@ class HipGoNet:
         # the updates that are a launch of their own, not part of grad_update
         self._own_update = (self.vel is not None or self.adam_m is not None
                             or self._clip is not None)
+        # ema_decay > 0: the moving average of the weights (seeded with them), the 16-byte
+        # record {int64 t; float omd; float pad} of applied averaging steps (two int64: the
+        # second holds omd) and the kernels' module (_dgema: ema.hip).  Training never reads it
+        self.ema = self.ema_rec = self._ema = None
+        self._ema_in = None          # inside ema_weights(): (address shift, its table)
+        if cfg.ema_decay > 0:
+            self._ema = ema()
+            self.ema = self.params.clone()
+            self.ema_rec = torch.zeros(2, dtype=torch.int64, device=dev)
+            # both launches behind a closed gate (they return at once and t stays 0): the
+            # module's code object is loaded here, not inside the capture of a step graph
+            self._ema_step(torch.zeros(1, device=dev).data_ptr(), stream_handle())
         # non-finite loss guard (cfg.nan_policy == "skip"): device gate read by the optimizer
         self.gate = torch.ones(1, dtype=torch.float32, device=dev)
         self._gate_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # finite_gate1
@@ -1304,12 +1320,13 @@ class HipGoNet:
 
     def forward(self):
         s = stream_handle()
-        self._run(self._pre, s)
-        self._run(self._fwd, s)
+        self._run(self._on_ema(self._pre), s)
+        self._run(self._on_ema(self._fwd), s)
 
     def forward_backward(self):
         """Loss/pred into self.loss/self.pred; gradients (mean over global batch) in
         self.grads.  Registered grad hooks fire right after their layer's wgrad."""
+        self._refuse_in_ema("forward_backward")
         s = stream_handle()
         # (no gradient zeroing: every gradient entry is written — not accumulated — by the
         # slab reduces and the deterministic head reduce)
@@ -1477,7 +1494,7 @@ class HipGoNet:
 
     def evaluate(self):
         self.forward()
-        self._head_eval.fn(*self._head_eval.args, stream_handle())
+        self._run(self._on_ema([self._head_eval]), stream_handle())
 
     # ------------------------------------------------------------------ prediction
     # the log-probabilities of the whole batch, for deep_go_amd.predict: allocated and planned
@@ -1509,7 +1526,7 @@ class HipGoNet:
         if self._head_predict is None or self._head_predict_in != self.cur_in:
             self.enable_predict()
         self.forward()
-        self._run([self._head_predict], stream_handle())
+        self._run(self._on_ema([self._head_predict]), stream_handle())
         return self.logp
 
     def optimizer_step(self, grad_scale: float = 1.0):
@@ -1519,7 +1536,10 @@ class HipGoNet:
         SGD / RMSProp and weight-refresh launches.  optimizer=momentum | adamw: their own
         launch(es) in the place of the SGD launch, then the weight refresh and LR decay.
         grad_clip > 0: the clip's two launches in front of the optimizer's, which is then a
-        separate launch for sgd | rmsprop too and reads the fp32 gradient."""
+        separate launch for sgd | rmsprop too and reads the fp32 gradient.  ema_decay > 0: the
+        average's two launches behind the last launch that writes the parameters, on either
+        path."""
+        self._refuse_in_ema("optimizer_step")
         s = stream_handle()
         n = self.layout.numel
         gate = self.gate.data_ptr() if self.cfg.nan_policy != "raise" else 0
@@ -1567,6 +1587,8 @@ class HipGoNet:
             t = self._step_refresh_table()
             self.h.weight_refresh_decay(t.ctypes.data, len(t), self.lr.data_ptr(),
                                         float(self.cfg.rateDecay), self.step_count.data_ptr(), s)
+            if self._ema is not None:
+                self._ema_step(gate, s)
             return
         t = self._gu_table(slabs)
         hd = self.head
@@ -1578,6 +1600,10 @@ class HipGoNet:
             plain = (0, 0)
         self._early_issued = False
         self._gu_launch(t, plain, grad_scale, gate, 1, s)
+        if self._ema is not None:
+            # (the gate of a deferred step is its loss check: an applied step averages the
+            # parameters as grad_update left them)
+            self._ema_step(gate, s)
 
     def _adamw(self, fn, g, grad_scale, gate, s):
         """optimizer=adamw's two launches (the count's, then the update): optim.hip."""
@@ -1603,6 +1629,84 @@ class HipGoNet:
         steps that clipped so far, from the device record.  Syncs."""
         norm, scale = self.clip_rec[0:1].view(torch.float32).tolist()
         return norm, scale, int(self.clip_rec[1].item())
+
+    # ------------------------------------------------------------------ weight average
+    def _ema_step(self, gate, s):
+        """ema_decay > 0's two launches (the count's, then the average): ema.hip."""
+        self._ema.ema(self.params.data_ptr(), self.ema.data_ptr(), self.params.numel(),
+                      self.ema_rec.data_ptr(), float(self.cfg.ema_decay), gate, s)
+
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("no weight average: ema_decay is 0")
+
+    def ema_steps(self) -> int:
+        """ema_decay > 0: the averaging steps applied so far (skipped ones do not count).
+        Syncs."""
+        self._need_ema()
+        return int(self.ema_rec[0].item())
+
+    def set_ema_steps(self, t: int):
+        self._need_ema()
+        self.ema_rec.zero_()           # (omd is rewritten before every use)
+        self.ema_rec[0] = int(t)
+
+    def reset_ema(self):
+        """ema_decay > 0: average = the parameters as they stand, no step applied."""
+        if self.ema is not None:
+            self.ema.copy_(self.params)
+            self.set_ema_steps(0)
+
+    def _refuse_in_ema(self, what: str):
+        if self._ema_in is not None:
+            raise RuntimeError(f"{what} inside ema_weights()")
+
+    def _on_ema(self, ops):
+        """Inside ema_weights(): the launches with every address into the flat parameter
+        vector (biases and head weights read in place) moved to the same element of the
+        average.  Outside: ops."""
+        if self._ema_in is None:
+            return ops
+        delta = self._ema_in[0]
+        lo = self.params.data_ptr()
+        hi = lo + 4 * self.params.numel()
+        return [op and dataclasses.replace(op, args=tuple(
+            x + delta if type(x) is int and lo <= x < hi else x for x in op.args))
+            for op in ops]
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """evaluate() / predict_logp() on the moving average instead of the weights.
+
+        Entering rewrites the operand copies (bf16 / e4m3 weights, bias tables) from the
+        average: weight_refresh with a twin of the full refresh table whose master-weight
+        columns point into ``self.ema``; the launches that read biases or head weights in place
+        get the same shift (_on_ema).  Leaving rewrites them from the weights, so the net is
+        then bit for bit the net that never entered.  fp8: the average is quantised with the
+        live weight scales (a value above 448 x s_w is clamped; fp8_update_scales does not
+        run), and the activation amaxes its forwards observe are put back on leaving.  Does not
+        nest; forward_backward and optimizer_step raise inside it."""
+        self._need_ema()
+        if self._ema_in is not None:
+            raise RuntimeError("ema_weights() does not nest")
+        if not self._fp8_calibrated:
+            raise RuntimeError("ema_weights() before the fp8 scales are calibrated")
+        delta = self.ema.data_ptr() - self.params.data_ptr()
+        twin = self._refresh_table.copy()
+        for col in RT_MASTER:
+            twin[:, col] += delta
+        twin = np.ascontiguousarray(twin)
+        amax = self.fp8_amax.clone() if self.fp8 else None
+        self.h.weight_refresh(twin.ctypes.data, len(twin), stream_handle())
+        self._ema_in = (delta, twin)
+        try:
+            yield self
+        finally:
+            self._ema_in = None
+            self.h.weight_refresh(self._refresh_table.ctypes.data, len(self._refresh_table),
+                                  stream_handle())
+            if amax is not None:
+                self.fp8_amax.copy_(amax)
 
     def adam_steps(self) -> int:
         """optimizer=adamw: the steps applied so far (skipped ones do not count).  Syncs."""
@@ -1755,6 +1859,7 @@ class HipGoNet:
     def train_step(self):
         """forward + backward + update; the gradient pass 2 deferred into the fused update
         when can_defer() holds (self.grads is then written by that launch)."""
+        self._refuse_in_ema("train_step")
         self.set_defer(True)
         try:
             self.forward_backward()
@@ -1772,6 +1877,7 @@ class HipGoNet:
     def load_params(self, flat: torch.Tensor):
         self.params.copy_(flat.to(self.params.device, torch.float32))
         self.refresh_weights()
+        self.reset_ema()
 
 
 class SegmentedStep:

@@ -76,9 +76,13 @@ class Predictor:
             self.params = flat_params.detach().float().cpu().contiguous()
 
     @classmethod
-    def load(cls, checkpoint: str, **kw) -> "Predictor":
-        from .utils.checkpoint import load_checkpoint
-        cfg, flat, _, _ = load_checkpoint(checkpoint)
+    def load(cls, checkpoint: str, ema: bool = False, **kw) -> "Predictor":
+        """ema: predict with the checkpoint's moving average of the weights (ema_decay > 0)
+        instead of its parameters; a checkpoint without one raises ValueError."""
+        from .utils.checkpoint import ema_params, load_checkpoint
+        cfg, flat, _, opt = load_checkpoint(checkpoint)
+        if ema:
+            flat = ema_params(checkpoint, flat, opt)
         return cls(cfg, flat, **kw)
 
     # ------------------------------------------------------------------ GPU

@@ -8,6 +8,11 @@ Both expose the same small surface used by the training loop:
   loss_sum() / correct()     of the last forward (host floats; synchronising)
   clip_stats()               grad_clip > 0: (grad_norm, clip_scale, clipped_steps) of the last
                              applied step and of the run (synchronising)
+  ema_params() / ema_steps() ema_decay > 0: the moving average of the weights (on the host) and
+                             the count of averaging steps applied
+  ema_weights()              ema_decay > 0: a context manager inside which evaluate() runs on
+                             the average; no training step may run inside it
+  reset_ema()                ema_decay > 0: average = parameters, no step applied
   params / rate / state_dict / load_state_dict
 
 ``load_next(loader)`` feeds the next training batch; with ``cfg.augment == "d4"`` it moves every
@@ -23,6 +28,7 @@ same bytes either way.  ``set_batch`` (validation, eval, predict) is never augme
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -35,7 +41,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, AdamW, Momentum, RMSProp, clip_grad_
+from .optim import SGD, AdamW, Momentum, RMSProp, WeightEMA, clip_grad_
 
 
 def _np(x, dtype):
@@ -79,6 +85,9 @@ class CPUBackend:
                              self.layout.weight_ranges())
         else:
             self.opt = SGD(cfg.rate, cfg.rateDecay)
+        # ema_decay > 0: the moving average of the weights, seeded with them
+        self.ema = WeightEMA(cfg.ema_decay, self.params) if cfg.ema_decay > 0 else None
+        self._ema_on = False          # inside ema_weights(): evaluate() reads the average
         self._x = None
         self._y = None
         self._loss_sum = 0.0
@@ -111,9 +120,12 @@ class CPUBackend:
         self._y = torch.from_numpy(_np(labels, np.int64))
 
     def _forward(self, x):
-        return reference_forward(self.layout, self.params, x, head_relu=self.cfg.head_relu)
+        w = self.ema.ema if self._ema_on else self.params
+        return reference_forward(self.layout, w, x, head_relu=self.cfg.head_relu)
 
     def forward_backward(self):
+        if self._ema_on:
+            raise RuntimeError("forward_backward inside ema_weights()")
         if self.params.grad is not None:
             self.params.grad.zero_()
         logp = self._forward(self._x)
@@ -137,13 +149,16 @@ class CPUBackend:
         self.optimizer_step()
 
     def optimizer_step(self):
+        if self._ema_on:
+            raise RuntimeError("optimizer_step inside ema_weights()")
         # skip on non-finite (all-reduced) gradients: every rank sees the same reduced
         # gradient, so all ranks skip together (a rank-local loss check would not)
         if self.cfg.nan_policy != "raise" and not (
                 np.isfinite(self._loss_sum) if self.world == 1
                 else bool(torch.isfinite(self.params.grad).all())):
             self.nan_skipped += 1
-            # (nothing of the optimizer's state moves: AdamW's count of applied steps neither)
+            # (nothing of the optimizer's state moves: AdamW's count of applied steps neither,
+            # nor the weight average and its count)
             self.opt.rate = self.opt.rate * (1.0 - getattr(self.opt, "rate_decay", 0.0))
             return
         with torch.no_grad():
@@ -151,6 +166,8 @@ class CPUBackend:
                 norm, scale = clip_grad_(self.params.grad, self.cfg.grad_clip)
                 self._clip = (norm, scale, self._clip[2] + (scale < 1.0))
             self.opt.step(self.params, self.params.grad)
+            if self.ema is not None:
+                self.ema.step(self.params)
 
     @torch.no_grad()
     def evaluate(self, n: Optional[int] = None):
@@ -182,18 +199,58 @@ class CPUBackend:
         applied steps that clipped so far."""
         return self._clip
 
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("no weight average: ema_decay is 0")
+
+    def ema_params(self) -> torch.Tensor:
+        """ema_decay > 0: the moving average of the weights."""
+        self._need_ema()
+        return self.ema.ema
+
+    def ema_steps(self) -> int:
+        """ema_decay > 0: the averaging steps applied so far (skipped ones do not count)."""
+        self._need_ema()
+        return self.ema.t
+
+    def reset_ema(self):
+        """ema_decay > 0: average = the parameters as they stand, no step applied."""
+        if self.ema is not None:
+            self.ema.reset(self.params)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """evaluate() on the moving average instead of the weights.  Does not nest; no
+        training step may run inside it."""
+        self._need_ema()
+        if self._ema_on:
+            raise RuntimeError("ema_weights() does not nest")
+        self._ema_on = True
+        try:
+            yield self
+        finally:
+            self._ema_on = False
+
     def flat_params(self) -> torch.Tensor:
         return self.params.detach()
 
     def load_params(self, flat: torch.Tensor):
         with torch.no_grad():
             self.params.copy_(flat.float())
+        self.reset_ema()
 
     def state_dict(self):
-        return {"optimizer": self.opt.state_dict()}
+        d = {"optimizer": self.opt.state_dict()}
+        if self.ema is not None:
+            # (ema_t is an integer: it travels in the checkpoint's metadata)
+            d["optimizer"].update(self.ema.state_dict())
+        return d
 
     def load_state_dict(self, d):
         self.opt.load_state_dict(d["optimizer"])
+        if self.ema is not None:
+            # (a checkpoint without an average: seeded from the parameters, t = 0)
+            self.ema.load_state_dict(d["optimizer"], self.params)
 
 
 class HIPBackend:
@@ -213,6 +270,8 @@ class HIPBackend:
         if world > 1 and flat is None:
             dp.broadcast_(self.net.params, 0)
             self.net.refresh_weights()
+            # (the average was seeded with this rank's own initial parameters)
+            self.net.reset_ema()
         self.bucketer = None
         self.comm = None
         if world > 1:
@@ -266,16 +325,19 @@ class HIPBackend:
                            t(rank, None).to(dev), t(labels, None).to(dev, torch.int32))
 
     def forward_backward(self):
+        self.net._refuse_in_ema("forward_backward")
         self._step.forward_backward()
         self._last = "train"
 
     def train_step(self):
         """forward_backward + optimizer_step with nothing in between: without DP buckets
         SegmentedStep replays both as ONE hipGraph (no graph boundary before the update)."""
+        self.net._refuse_in_ema("train_step")
         self._step()
         self._last = "train"
 
     def optimizer_step(self):
+        self.net._refuse_in_ema("optimizer_step")
         self._step.optimizer()
 
     def evaluate(self, n: Optional[int] = None):
@@ -313,6 +375,25 @@ class HIPBackend:
         applied steps that clipped so far, from the device record (syncs)."""
         return self.net.clip_stats()
 
+    def ema_params(self) -> torch.Tensor:
+        """ema_decay > 0: the moving average of the weights, on the host (syncs)."""
+        self.net._need_ema()
+        return self.net.ema.detach().cpu()
+
+    def ema_steps(self) -> int:
+        """ema_decay > 0: the averaging steps applied so far (skipped ones do not count).
+        Syncs."""
+        return self.net.ema_steps()
+
+    def reset_ema(self):
+        """ema_decay > 0: average = the parameters as they stand, no step applied."""
+        self.net.reset_ema()
+
+    def ema_weights(self):
+        """A context manager inside which evaluate() runs on the moving average
+        (HipGoNet.ema_weights: the operand copies are swapped; no training step inside)."""
+        return self.net.ema_weights()
+
     def flat_params(self) -> torch.Tensor:
         return self.net.params.detach().cpu()
 
@@ -331,6 +412,9 @@ class HIPBackend:
             d["optimizer"]["adam_v"] = self.net.adam_v.detach().cpu()
             # (an integer: it travels in the checkpoint's metadata, not as a float tensor)
             d["optimizer"]["adam_t"] = self.net.adam_steps()
+        if self.net.ema is not None:
+            d["optimizer"]["ema"] = self.net.ema.detach().cpu()
+            d["optimizer"]["ema_t"] = self.net.ema_steps()
         return d
 
     def close(self):
@@ -357,3 +441,10 @@ class HIPBackend:
                 t = getattr(self.net, name)
                 t.copy_(o[name].to(t.device)) if has else t.zero_()
             self.net.set_adam_steps(int(o.get("adam_t", 0)) if has else 0)
+        if self.net.ema is not None:
+            # (a checkpoint without an average: seeded from the parameters, t = 0)
+            if "ema" in o:
+                self.net.ema.copy_(o["ema"].to(self.net.ema.device))
+                self.net.set_ema_steps(int(o.get("ema_t", 0)))
+            else:
+                self.net.reset_ema()

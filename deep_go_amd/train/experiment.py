@@ -18,6 +18,7 @@ Reference map:
 from __future__ import annotations
 
 import collections
+import contextlib
 import os
 import time
 from typing import Dict, List, Optional
@@ -100,6 +101,8 @@ class Experiment:
                                       board0=info.rank * self.local_batch)
             if world > 1 and self._restore_params is None:
                 dp.broadcast_(self.backend.params.data, 0)
+                # (the average was seeded with this rank's own initial parameters)
+                self.backend.reset_ema()
         if self._restore_opt is not None:
             self.backend.load_state_dict({"optimizer": self._restore_opt})
         self.sources = {s: self._source(s) for s in ("train", "validation")}
@@ -144,9 +147,14 @@ class Experiment:
         ld.close()
         return batch
 
-    def eval_batch_set(self, data, quirks: Optional[bool] = None):
+    def eval_batch_set(self, data, quirks: Optional[bool] = None, ema: bool = False):
         """(cost, accuracy) of a fixed sample set, chunked by the local batch size and sharded
-        across DP ranks (sums all-reduced)."""
+        across DP ranks (sums all-reduced).  ema: on the moving average of the weights
+        (ema_decay > 0) instead of the weights."""
+        with self.backend.ema_weights() if ema else contextlib.nullcontext():
+            return self._eval_batch_set(data, quirks)
+
+    def _eval_batch_set(self, data, quirks: Optional[bool]):
         quirks = self.cfg.reference_validation_quirks if quirks is None else quirks
         planes, player, rank, labels = data
         N = len(labels)
@@ -260,6 +268,12 @@ class Experiment:
                     self.metrics.line(f"validation at iteration {step}: cost={vc}, accuracy={va}")
                     self.metrics.record(kind="validation", step=step, val_cost=vc, val_acc=va,
                                         lr=lr_now)
+                    if cfg.ema_decay > 0:
+                        # the same sample set on the moving average of the weights
+                        with trace.range("validation_ema"):
+                            vce, vae = self.eval_batch_set(val, ema=True)
+                        self.metrics.record(kind="validation_ema", step=step, val_cost=vce,
+                                            val_acc=vae)
                     # the reference saves here, BEFORE this iteration's update (train.lua:124):
                     # that checkpoint pairs iteration N with N-1 updates.  We save after the
                     # update below so a resumed run continues bit-exactly (auto-resume).
@@ -356,8 +370,13 @@ class Experiment:
                               self.backend.rate)
 
     @classmethod
-    def load(cls, path: str, reset_optimizer: bool = False, **overrides) -> "Experiment":
+    def load(cls, path: str, reset_optimizer: bool = False, ema: bool = False,
+             **overrides) -> "Experiment":
+        """ema: the checkpoint's moving average in the place of its parameters (for eval; a
+        checkpoint without one raises ValueError)."""
         cfg, flat, state, opt = ckpt.load_checkpoint(path)
+        if ema:
+            flat = ckpt.ema_params(path, flat, opt)
         if overrides:
             cfg = cfg.replace(**overrides)
         e = cls(cfg, id=state.get("id"))

@@ -26,6 +26,14 @@
 norm = |gscale| * sqrt(sum g^2), scale = min(1, c / (norm + 1e-6)), g *= scale, which is
 ``torch.nn.utils.clip_grad_norm_(params, c)`` applied to g * gscale (the GPU path:
 csrc/kernels/clip.hip).
+
+``WeightEMA`` (an addition; ``ema_decay`` > 0) runs after them, once per applied step, and is
+read by nothing in training: with the average e (the parameters at the start) and t, the count
+of applied averaging steps (0 at the start): t += 1; d = min(ema_decay, (1 + t) / (10 + t)) in
+double (the ramp is the usual warm-up: a short run is not dominated by the initialisation);
+omd = fp32(1 - d); e = fmaf(omd, theta - e, e) in fp32, theta as the update left it.  The lerp
+form makes e == theta a fixed point and keeps the result between e and theta.  A skipped step is
+no call of ``step`` (the GPU path: csrc/kernels/ema.hip).
 """
 from __future__ import annotations
 
@@ -165,3 +173,59 @@ class AdamW:
         self.m = d["adam_m"].float().clone() if has else torch.zeros_like(self.m)
         self.v = d["adam_v"].float().clone() if has else torch.zeros_like(self.v)
         self.t = int(d.get("adam_t", 0)) if has else 0
+
+
+def ema_omd(decay: float, t: int) -> float:
+    """1 - min(decay, (1 + t) / (10 + t)) as the fp32 value averaging step t uses (t counts from
+    1; every operation in double, then one rounding)."""
+    td = float(t)
+    return float(np.float32(1.0 - min(float(decay), (1.0 + td) / (10.0 + td))))
+
+
+def fma32(a, b: np.ndarray, c: np.ndarray) -> np.ndarray:
+    """fmaf(a, b, c) on fp32 arrays with its single rounding.  The product of two fp32 values is
+    exact in double; the sum is brought to round-to-odd in double (TwoSum tells whether it was
+    exact and on which side the rest lies), and rounding that to fp32 is then the rounding of
+    the exact value (53 >= 2 * 24 + 2 bits)."""
+    a64 = np.asarray(a, dtype=np.float32).astype(np.float64)
+    prod = a64 * b.astype(np.float64)
+    c64 = c.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = prod + c64
+        bb = s - prod
+        err = (prod - (s - bb)) + (c64 - bb)
+        fix = np.isfinite(s) & (err != 0.0) & ((s.view(np.int64) & 1) == 0)
+        toward = np.where(err > 0.0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, toward), s)
+        return s.astype(np.float32)
+
+
+class WeightEMA:
+    def __init__(self, decay: float, params: torch.Tensor):
+        self.decay = float(decay)
+        self.reset(params)
+
+    @torch.no_grad()
+    def reset(self, params: torch.Tensor):
+        """e = the parameters, no averaging step applied."""
+        self.ema = params.detach().float().clone()
+        self.t = 0
+
+    @torch.no_grad()
+    def step(self, params: torch.Tensor):
+        self.t += 1
+        omd = np.float32(ema_omd(self.decay, self.t))
+        e = self.ema.numpy()
+        diff = params.detach().numpy() - e            # (one fp32 rounding)
+        e[...] = fma32(omd, diff, e)
+
+    def state_dict(self):
+        return {"ema": self.ema, "ema_t": int(self.t)}
+
+    def load_state_dict(self, d, params: torch.Tensor):
+        """(a checkpoint without an average: start from the parameters, t = 0)"""
+        if "ema" in d:
+            self.ema = d["ema"].float().clone()
+            self.t = int(d.get("ema_t", 0))
+        else:
+            self.reset(params)

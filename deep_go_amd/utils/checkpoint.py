@@ -69,6 +69,16 @@ def load_checkpoint(path: str) -> Tuple[ExperimentConfig, torch.Tensor, Dict, Di
     return cfg, flat, meta["state"], opt
 
 
+def ema_params(path: str, flat: torch.Tensor, optimizer: Dict[str, Any]) -> torch.Tensor:
+    """The moving average of the weights a checkpoint of an ``ema_decay > 0`` run carries
+    (``optimizer.ema``), shaped like its flat parameter vector; ValueError if it has none."""
+    e = optimizer.get("ema")
+    if not isinstance(e, torch.Tensor) or e.numel() != flat.numel():
+        raise ValueError(f"{path}: the checkpoint carries no weight average "
+                         "(train with ema_decay > 0)")
+    return e.float().reshape(flat.shape).clone()
+
+
 # ----------------------------------------------------------------------------- Torch7
 def _module(cls: str, **fields) -> Dict[str, Any]:
     d = {"__torch_class__": cls, "train": True}
