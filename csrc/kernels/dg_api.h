@@ -367,4 +367,15 @@ hipError_t dg_ema_tick(void* rec, double decay, const float* gate, hipStream_t s
 hipError_t dg_ema(const float* p, float* e, size_t n, void* rec, double decay, const float* gate,
                   hipStream_t s);
 
+// --------------------------------------------------------------- sched.hip (module _dgsched)
+// The learning-rate schedule: one launch (lr_sched_tick: one wave, one lane, NO gate: a skipped
+// step counts) on rec, the 16-byte device record {double base; int64 s} (8-byte aligned), and
+// lr, the rate the optimizer kernels read.  advance 1: base *= (1 - rate_decay); s += 1; *lr =
+// base * f(s).  advance 0: *lr = base * f(s) only.  f(s) = w(s) d(s) of
+// deep_go_amd/train/optim.py lr_factor; kind 0 constant | 1 linear | 2 cosine | 3 step; W >= 0,
+// T >= 0 (linear, cosine: T > W), m in [0, 1], E >= 0 (step: E > 0), g in (0, 1], rate_decay
+// finite; anything else is refused before any GPU work.
+hipError_t dg_lr_sched(void* rec, double* lr, int kind, long long W, long long T, double m,
+                       long long E, double g, double rate_decay, int advance, hipStream_t s);
+
 }  // extern "C"

@@ -6,11 +6,12 @@ Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
 ``deep_go_amd/_native/_dgadam<EXT>`` (the AdamW optimizer's kernels: the same optim.hip behind
 bindings of its own),
 ``deep_go_amd/_native/_dgclip<EXT>`` (gradient clipping by the global norm: clip.hip),
-``deep_go_amd/_native/_dgema<EXT>`` (the moving average of the weights: ema.hip) and
+``deep_go_amd/_native/_dgema<EXT>`` (the moving average of the weights: ema.hip),
+``deep_go_amd/_native/_dgsched<EXT>`` (the learning-rate schedule: sched.hip) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|clip|ema|cpu|comm]
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|clip|ema|sched|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -141,6 +142,12 @@ def build_ema(force: bool = False) -> Path:
     return _build_small("ema", "ema.hip", "ema_bindings.cpp", force)
 
 
+def build_sched(force: bool = False) -> Path:
+    """_dgsched: the learning-rate schedule's launch (sched.hip + sched_bindings.cpp), imported
+    only for lr_schedule != none and apart from the other modules for the same reason."""
+    return _build_small("sched", "sched.hip", "sched_bindings.cpp", force)
+
+
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
     BUILD.mkdir(exist_ok=True)
     OUT.mkdir(exist_ok=True)
@@ -198,13 +205,15 @@ def build_all(force: bool = False) -> None:
     build_adam(force)
     build_clip(force)
     build_ema(force)
+    build_sched(force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "clip", "ema", "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "clip", "ema", "sched", "cpu",
+                                       "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -222,6 +231,8 @@ def main(argv=None):
         print(build_clip(a.force))
     if a.only in (None, "ema") and not a.sanitize:
         print(build_ema(a.force))
+    if a.only in (None, "sched") and not a.sanitize:
+        print(build_sched(a.force))
     if a.only in (None, "comm") and not a.sanitize:
         print(build_comm(a.force))
 

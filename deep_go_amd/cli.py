@@ -31,9 +31,22 @@ import os
 import sys
 
 
-def _cfg_from(args, base=None):
+def _fill_lr_total(iters):
+    """train: lr_schedule=linear | cosine without an lr_total takes --iters as its horizon,
+    before the config is built (which refuses the schedule without one); it is then part of the
+    checkpoint's config, so a resumed run keeps it."""
+    def fill(ov):
+        if ov.get("lr_schedule") in ("linear", "cosine") and "lr_total" not in ov:
+            ov["lr_total"] = str(iters)
+        return ov
+    return fill
+
+
+def _cfg_from(args, base=None, fill=None):
     from .config import ExperimentConfig, get_preset, parse_overrides
     ov = parse_overrides(args.overrides)
+    if fill is not None:
+        ov = fill(ov)
     if base is not None:
         return base.replace(**ov) if ov else base
     if args.preset:
@@ -43,7 +56,7 @@ def _cfg_from(args, base=None):
 
 def cmd_train(args):
     from .train.experiment import Experiment
-    cfg = _cfg_from(args)
+    cfg = _cfg_from(args, fill=_fill_lr_total(args.iters))
     if args.device == "cpu":
         cfg = cfg.replace(useCuda=False)
     elif args.device == "gpu":

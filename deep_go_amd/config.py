@@ -24,6 +24,12 @@ Parity notes (reference = Torch7 ``vipmath/deep-go``):
   (10 + t)), e += (1 - d) (p - e).  Training never reads it; validation also reports it, and
   ``eval`` / ``predict`` / ``export`` ``--ema`` serve it.  ``override`` refuses a value outside
   [0, 1) and a NaN.
+* ``lr_schedule`` (an addition; ``none`` = off) multiplies the decaying rate by a warm-up and a
+  decay factor (train/optim.py LRSchedule): with base (``rate`` at the start) and s, the count of
+  steps taken, skipped ones included, step s uses base * (w(s) * d(s)); after every step base *=
+  (1 - rateDecay), s += 1.  ``lr_warmup``, ``lr_total``, ``lr_min``, ``lr_step_every`` and
+  ``lr_gamma`` are its parameters; ``override`` refuses one out of range and one set without a
+  schedule.
 """
 from __future__ import annotations
 
@@ -88,6 +94,15 @@ class ExperimentConfig:
     # the decay of the exponential moving average of the weights (0 = off; train/optim.py
     # WeightEMA), in [0, 1), valid with every optimizer; it changes nothing of the training itself
     ema_decay: float = 0.0
+    # the learning-rate schedule (train/optim.py LRSchedule): none | constant (warm-up, then
+    # flat) | linear | cosine | step, a factor on the rate that rateDecay decays, valid with
+    # every optimizer.  A field below set while lr_schedule=none is rejected, not ignored
+    lr_schedule: str = "none"
+    lr_warmup: int = 0             # W: warm-up steps, >= 0 (step s uses (s + 1) / W of the rate)
+    lr_total: int = 0              # T: the horizon in steps; linear | cosine need T > W
+    lr_min: float = 0.0            # m: the floor as a fraction of the base rate, in [0, 1]
+    lr_step_every: int = 0         # E: step multiplies by lr_gamma every E steps; it needs E > 0
+    lr_gamma: float = 0.1          # g: in (0, 1], for step only
     bucket_mb: float = 6.0         # DP gradient bucket size (12x128: head + hidden layers | layer 0)
     # DP all-reduce dtype: fp32 (the reference's DataParallelTable reduces fp32 gradients,
     # experiments.lua:155-168) | bf16 (opt-in: the wire twin every gradient pass 2 writes; half
@@ -208,7 +223,9 @@ def _coerce(name: str, value: Any, current: Any) -> Any:
 
 _CHOICES = {"nan_policy": ("guard", "skip", "raise"), "comm": ("auto", "native", "torch"),
             "optimizer": ("sgd", "rmsprop", "momentum", "adamw"), "grad_dtype": ("fp32", "bf16"),
-            "sampling": ("game", "position"), "augment": ("none", "d4")}
+            "sampling": ("game", "position"), "augment": ("none", "d4"),
+            "lr_schedule": ("none", "constant", "linear", "cosine", "step")}
+# (LR_KINDS below: the same names without none)
 
 
 def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
@@ -246,7 +263,38 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
         for k in ("adam_beta1", "adam_beta2", "adam_eps"):
             if getattr(new, k) != getattr(base, k):
                 raise ValueError(f"{k} needs optimizer=adamw, not optimizer={new.optimizer!r}")
+    _check_lr_schedule(new)
     return new
+
+
+# the schedules; a launch of csrc/kernels/sched.hip names one by its index here
+LR_KINDS = ("constant", "linear", "cosine", "step")
+LR_FIELDS = ("lr_warmup", "lr_total", "lr_min", "lr_step_every", "lr_gamma")
+
+
+def _check_lr_schedule(new: ExperimentConfig) -> None:
+    """The lr_* fields: their ranges (written so that a NaN is refused too), what each schedule
+    needs, and nothing set without a schedule (as nesterov without momentum)."""
+    for k in ("lr_warmup", "lr_total", "lr_step_every"):
+        v = getattr(new, k)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{k}={v!r}: expected an integer >= 0")
+    if not 0.0 <= new.lr_min <= 1.0:
+        raise ValueError(f"lr_min={new.lr_min!r}: expected a value in [0, 1]")
+    if not 0.0 < new.lr_gamma <= 1.0:
+        raise ValueError(f"lr_gamma={new.lr_gamma!r}: expected a value in (0, 1]")
+    kind = new.lr_schedule
+    if kind == "none":
+        base = ExperimentConfig()
+        for k in LR_FIELDS:
+            if getattr(new, k) != getattr(base, k):
+                raise ValueError(f"{k} needs an lr_schedule, not lr_schedule='none'")
+    if kind in ("linear", "cosine") and not new.lr_total > new.lr_warmup:
+        raise ValueError(f"lr_total={new.lr_total!r}: lr_schedule={kind} needs lr_total > "
+                         f"lr_warmup ({new.lr_warmup})")
+    if kind == "step" and not new.lr_step_every > 0:
+        raise ValueError(f"lr_step_every={new.lr_step_every!r}: lr_schedule=step needs a value "
+                         "> 0")
 
 
 def parse_overrides(items: List[str]) -> Dict[str, Any]:

@@ -28,10 +28,10 @@ from typing import Callable, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
-from ..config import NUM_POINTS, ExperimentConfig
+from ..config import LR_KINDS, NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import adam, clip, ema, hip, opt, stream_handle
+from ..ops.native import adam, clip, ema, hip, opt, sched, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -284,6 +284,17 @@ class HipGoNet:
             # both launches behind a closed gate (they return at once and t stays 0): the
             # module's code object is loaded here, not inside the capture of a step graph
             self._ema_step(torch.zeros(1, device=dev).data_ptr(), stream_handle())
+        # lr_schedule != none: the 16-byte record {double base; int64 s} (two int64: the first
+        # holds base) of the rate that rateDecay decays and the steps taken, skipped ones
+        # included, and the launch's module (_dgsched: sched.hip).  lr is always what the device
+        # formula gives: the advance = 0 launch writes it here (which also loads the module's
+        # code object outside any capture of a step graph)
+        self.lr_rec = self._sched = None
+        if cfg.lr_schedule != "none":
+            self._sched = sched()
+            self._sched_kind = LR_KINDS.index(cfg.lr_schedule)
+            self.lr_rec = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.reset_lr_schedule()
         # non-finite loss guard (cfg.nan_policy == "skip"): device gate read by the optimizer
         self.gate = torch.ones(1, dtype=torch.float32, device=dev)
         self._gate_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # finite_gate1
@@ -1538,7 +1549,10 @@ class HipGoNet:
         grad_clip > 0: the clip's two launches in front of the optimizer's, which is then a
         separate launch for sgd | rmsprop too and reads the fp32 gradient.  ema_decay > 0: the
         average's two launches behind the last launch that writes the parameters, on either
-        path."""
+        path.  lr_schedule != none: the schedule's launch last of all, behind the launch that
+        decays lr (it takes no gate: a skipped step counts), so that every reader of lr in the
+        next step, the early grad_update of a deferred step included, sees the scheduled
+        rate."""
         self._refuse_in_ema("optimizer_step")
         s = stream_handle()
         n = self.layout.numel
@@ -1589,6 +1603,8 @@ class HipGoNet:
                                         float(self.cfg.rateDecay), self.step_count.data_ptr(), s)
             if self._ema is not None:
                 self._ema_step(gate, s)
+            if self._sched is not None:
+                self._lr_tick(1, s)
             return
         t = self._gu_table(slabs)
         hd = self.head
@@ -1604,6 +1620,8 @@ class HipGoNet:
             # (the gate of a deferred step is its loss check: an applied step averages the
             # parameters as grad_update left them)
             self._ema_step(gate, s)
+        if self._sched is not None:
+            self._lr_tick(1, s)
 
     def _adamw(self, fn, g, grad_scale, gate, s):
         """optimizer=adamw's two launches (the count's, then the update): optim.hip."""
@@ -1707,6 +1725,38 @@ class HipGoNet:
                                   stream_handle())
             if amax is not None:
                 self.fp8_amax.copy_(amax)
+
+    # ------------------------------------------------------------------ learning-rate schedule
+    def _lr_tick(self, advance: int, s):
+        """lr_schedule != none's launch (sched.hip): advance 1: base *= (1 - rateDecay), s += 1;
+        either way lr = base * factor(s)."""
+        c = self.cfg
+        self._sched.lr_sched(self.lr_rec.data_ptr(), self.lr.data_ptr(), self._sched_kind,
+                             int(c.lr_warmup), int(c.lr_total), float(c.lr_min),
+                             int(c.lr_step_every), float(c.lr_gamma), float(c.rateDecay),
+                             advance, s)
+
+    def _need_sched(self):
+        if self.lr_rec is None:
+            raise RuntimeError("no learning-rate schedule: lr_schedule is none")
+
+    def lr_schedule_state(self):
+        """lr_schedule != none: (base, s), the rate that rateDecay decays and the steps taken so
+        far, skipped ones included.  Syncs."""
+        self._need_sched()
+        return float(self.lr_rec[0:1].view(torch.float64).item()), int(self.lr_rec[1].item())
+
+    def set_lr_schedule_state(self, base: float, s: int):
+        """base and s as given; lr is rewritten on the device from them."""
+        self._need_sched()
+        self.lr_rec[0:1].view(torch.float64).fill_(float(base))
+        self.lr_rec[1] = int(s)
+        self._lr_tick(0, stream_handle())
+
+    def reset_lr_schedule(self):
+        """lr_schedule != none: base = cfg.rate, s = 0 (a warm restart)."""
+        if self.lr_rec is not None:
+            self.set_lr_schedule_state(float(self.cfg.rate), 0)
 
     def adam_steps(self) -> int:
         """optimizer=adamw: the steps applied so far (skipped ones do not count).  Syncs."""

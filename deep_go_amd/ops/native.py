@@ -5,7 +5,9 @@
 ``_dgopt`` module (the momentum optimizer's kernel), imported only for it; ``adam()`` the
 ``_dgadam`` module (the AdamW optimizer's kernels), likewise; ``clip()`` the ``_dgclip`` module
 (gradient clipping by the global norm), imported only for ``grad_clip > 0``; ``ema()`` the
-``_dgema`` module (the moving average of the weights), imported only for ``ema_decay > 0``.  On a machine
+``_dgema`` module (the moving average of the weights), imported only for ``ema_decay > 0``;
+``sched()`` the ``_dgsched`` module (the learning-rate schedule's launch), imported only for
+``lr_schedule != none``.  On a machine
 with a GPU a missing or stale extension is a hard error — there is deliberately no silent
 PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
 SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
@@ -41,6 +43,7 @@ def _load(name: str):
             {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
              "_dgopt": _build.build_opt, "_dgadam": _build.build_adam,
              "_dgclip": _build.build_clip, "_dgema": _build.build_ema,
+             "_dgsched": _build.build_sched,
              "_dgcomm": _build.build_comm}.get(
                 name, _build.build_cpu)()
             mod = importlib.import_module(name)
@@ -79,6 +82,11 @@ def clip():
 def ema():
     """_dgema: the exponential moving average of the weights (csrc/kernels/ema.hip)."""
     return _load("_dgema")
+
+
+def sched():
+    """_dgsched: the learning-rate schedule's launch (csrc/kernels/sched.hip)."""
+    return _load("_dgsched")
 
 
 def cpu():

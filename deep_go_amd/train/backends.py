@@ -13,7 +13,12 @@ Both expose the same small surface used by the training loop:
   ema_weights()              ema_decay > 0: a context manager inside which evaluate() runs on
                              the average; no training step may run inside it
   reset_ema()                ema_decay > 0: average = parameters, no step applied
-  params / rate / state_dict / load_state_dict
+  rate                       the rate the next step will use (with an lr_schedule: the scheduled
+                             one)
+  base_rate / lr_step        lr_schedule != none: the rate that rateDecay decays, which the
+                             schedule's factor multiplies, and the steps taken so far, skipped
+                             ones included (without a schedule: rate and 0)
+  params / state_dict / load_state_dict
 
 ``load_next(loader)`` feeds the next training batch; with ``cfg.augment == "d4"`` it moves every
 board by the symmetry ``data/symmetry.py augment_symmetries(cfg.seed, seq, board0 + i)`` draws
@@ -41,7 +46,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, AdamW, Momentum, RMSProp, WeightEMA, clip_grad_
+from .optim import SGD, AdamW, LRSchedule, Momentum, RMSProp, WeightEMA, clip_grad_
 
 
 def _np(x, dtype):
@@ -85,6 +90,12 @@ class CPUBackend:
                              self.layout.weight_ranges())
         else:
             self.opt = SGD(cfg.rate, cfg.rateDecay)
+        # lr_schedule != none: base and s live here; the optimizer's rate is rewritten from them
+        # after every step, so its own rate *= never compounds with the factor
+        self.sched = None
+        if cfg.lr_schedule != "none":
+            self.sched = LRSchedule(cfg, getattr(self.opt, "rate_decay", 0.0))
+            self.opt.rate = self.sched.rate
         # ema_decay > 0: the moving average of the weights, seeded with them
         self.ema = WeightEMA(cfg.ema_decay, self.params) if cfg.ema_decay > 0 else None
         self._ema_on = False          # inside ema_weights(): evaluate() reads the average
@@ -106,6 +117,20 @@ class CPUBackend:
     @property
     def rate(self) -> float:
         return self.opt.rate
+
+    @property
+    def base_rate(self) -> float:
+        return self.sched.base if self.sched is not None else self.opt.rate
+
+    @property
+    def lr_step(self) -> int:
+        return self.sched.s if self.sched is not None else 0
+
+    def _sched_step(self):
+        """lr_schedule != none, after every step, applied or skipped: base takes the decay, s
+        counts, and the rate is rewritten from them."""
+        self.sched.step()
+        self.opt.rate = self.sched.rate
 
     def load_next(self, loader):
         seq = loader.consumed          # the sequence number of the batch about to be taken
@@ -159,13 +184,18 @@ class CPUBackend:
             self.nan_skipped += 1
             # (nothing of the optimizer's state moves: AdamW's count of applied steps neither,
             # nor the weight average and its count)
-            self.opt.rate = self.opt.rate * (1.0 - getattr(self.opt, "rate_decay", 0.0))
+            if self.sched is not None:
+                self._sched_step()
+            else:
+                self.opt.rate = self.opt.rate * (1.0 - getattr(self.opt, "rate_decay", 0.0))
             return
         with torch.no_grad():
             if self.cfg.grad_clip > 0:
                 norm, scale = clip_grad_(self.params.grad, self.cfg.grad_clip)
                 self._clip = (norm, scale, self._clip[2] + (scale < 1.0))
             self.opt.step(self.params, self.params.grad)
+            if self.sched is not None:
+                self._sched_step()
             if self.ema is not None:
                 self.ema.step(self.params)
 
@@ -241,6 +271,10 @@ class CPUBackend:
 
     def state_dict(self):
         d = {"optimizer": self.opt.state_dict()}
+        if self.sched is not None:
+            # rate holds base (resumed with the schedule off, a run continues from the undamped
+            # rate); lr_step is an integer: it travels in the checkpoint's metadata
+            d["optimizer"].update(self.sched.state_dict())
         if self.ema is not None:
             # (ema_t is an integer: it travels in the checkpoint's metadata)
             d["optimizer"].update(self.ema.state_dict())
@@ -248,6 +282,10 @@ class CPUBackend:
 
     def load_state_dict(self, d):
         self.opt.load_state_dict(d["optimizer"])
+        if self.sched is not None:
+            # (a checkpoint without lr_step: base = its rate, s = 0)
+            self.sched.load_state_dict(d["optimizer"])
+            self.opt.rate = self.sched.rate
         if self.ema is not None:
             # (a checkpoint without an average: seeded from the parameters, t = 0)
             self.ema.load_state_dict(d["optimizer"], self.params)
@@ -299,6 +337,14 @@ class HIPBackend:
     @property
     def rate(self) -> float:
         return float(self.net.lr.item())
+
+    @property
+    def base_rate(self) -> float:
+        return self.net.lr_schedule_state()[0] if self.net.lr_rec is not None else self.rate
+
+    @property
+    def lr_step(self) -> int:
+        return self.net.lr_schedule_state()[1] if self.net.lr_rec is not None else 0
 
     @property
     def params(self):
@@ -403,6 +449,10 @@ class HIPBackend:
     def state_dict(self):
         d = {"optimizer": {"kind": self.cfg.optimizer, "rate": self.rate,
                            "rate_decay": self.cfg.rateDecay}}
+        if self.net.lr_rec is not None:
+            # rate holds base (resumed with the schedule off, a run continues from the undamped
+            # rate); lr_step is an integer: it travels in the checkpoint's metadata
+            d["optimizer"]["rate"], d["optimizer"]["lr_step"] = self.net.lr_schedule_state()
         if self.net.ms is not None:
             d["optimizer"]["ms"] = self.net.ms.detach().cpu()
         if self.net.vel is not None:
@@ -426,6 +476,10 @@ class HIPBackend:
     def load_state_dict(self, d):
         o = d["optimizer"]
         self.net.lr.fill_(float(o["rate"]))
+        if self.net.lr_rec is not None:
+            # (a checkpoint without lr_step: base = its rate, s = 0); lr is then rewritten on
+            # the device from them
+            self.net.set_lr_schedule_state(float(o["rate"]), int(o.get("lr_step", 0)))
         if "ms" in o and self.net.ms is not None:
             self.net.ms.copy_(o["ms"].to(self.net.ms.device))
         if self.net.vel is not None:

@@ -295,6 +295,11 @@ class Experiment:
                     gn, cs, nclip = be.clip_stats()
                     self.metrics.record(kind="clip", step=step, grad_norm=gn, clip_scale=cs,
                                         clipped_steps=nclip)
+                if cfg.lr_schedule != "none" and step % cfg.log_interval == 0:
+                    # (after the update: the schedule's state as the next step finds it, rate =
+                    # base_rate * factor(lr_step))
+                    self.metrics.record(kind="lr", step=step, rate=be.rate,
+                                        base_rate=be.base_rate, lr_step=be.lr_step)
                 # (after the update: the device's skip counter then includes this step)
                 if skipguard is not None:
                     skipguard.step()

@@ -34,11 +34,19 @@ double (the ramp is the usual warm-up: a short run is not dominated by the initi
 omd = fp32(1 - d); e = fmaf(omd, theta - e, e) in fp32, theta as the update left it.  The lerp
 form makes e == theta a fixed point and keeps the result between e and theta.  A skipped step is
 no call of ``step`` (the GPU path: csrc/kernels/ema.hip).
+
+``LRSchedule`` (an addition; ``lr_schedule`` != none) owns the rate: the optimizers' own decay
+of it is overwritten after every step, applied or skipped, with base * factor(s), where base
+takes that decay in their place (the GPU path: csrc/kernels/sched.hip).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
+
+from ..config import LR_KINDS
 
 
 @torch.no_grad()
@@ -229,3 +237,67 @@ class WeightEMA:
             self.t = int(d.get("ema_t", 0))
         else:
             self.reset(params)
+
+
+def lr_factor(kind: str, s: int, W: int, T: int, m: float, E: int, g: float) -> float:
+    """w(s) * d(s) of step s (counted from 0), every operation in double:
+    w = min(1, (s + 1) / W) for W > 0, else 1; u = clamp((s - W) / (T - W), 0, 1);
+    d = 1 (constant) | 1 - (1 - m) u (linear) | m + (1 - m) 0.5 (1 + cos(pi u)) (cosine), and
+    exactly m for s >= T for both | max(m, g ** floor(max(s - W, 0) / E)) (step)."""
+    s, m, g = int(s), float(m), float(g)
+    w = min(1.0, (s + 1.0) / float(W)) if W > 0 else 1.0
+    if kind == "constant":
+        d = 1.0
+    elif kind in ("linear", "cosine"):
+        if s >= T:
+            d = m                      # (past the horizon the factor stays at the floor)
+        else:
+            u = min(max(float(s - W) / float(T - W), 0.0), 1.0)
+            if kind == "linear":
+                d = 1.0 - (1.0 - m) * u
+            else:
+                d = m + (1.0 - m) * (0.5 * (1.0 + math.cos(math.pi * u)))
+    elif kind == "step":
+        d = max(m, g ** float(max(s - W, 0) // E))
+    else:
+        raise ValueError(f"lr_schedule {kind!r}")
+    return w * d
+
+
+class LRSchedule:
+    """``lr_schedule`` != none: base (cfg.rate at the start; it carries the rateDecay) and s (the
+    steps taken so far, skipped ones included).  The rate step s uses is base * factor(s)."""
+
+    def __init__(self, cfg, rate_decay: float = None):
+        self.kind = cfg.lr_schedule
+        if self.kind not in LR_KINDS:
+            raise ValueError(f"lr_schedule {self.kind!r}")
+        self.W, self.T, self.E = int(cfg.lr_warmup), int(cfg.lr_total), int(cfg.lr_step_every)
+        self.m, self.g = float(cfg.lr_min), float(cfg.lr_gamma)
+        self.rate0 = float(cfg.rate)
+        self.rate_decay = float(cfg.rateDecay if rate_decay is None else rate_decay)
+        self.reset()
+
+    def reset(self):
+        self.base, self.s = self.rate0, 0
+
+    def factor(self, s: int) -> float:
+        return lr_factor(self.kind, s, self.W, self.T, self.m, self.E, self.g)
+
+    @property
+    def rate(self) -> float:
+        """The rate the next step uses."""
+        return self.base * self.factor(self.s)
+
+    def step(self):
+        """After every step, applied or skipped."""
+        self.base = self.base * (1.0 - self.rate_decay)
+        self.s += 1
+
+    def state_dict(self):
+        return {"rate": self.base, "lr_step": int(self.s)}
+
+    def load_state_dict(self, d):
+        """(a checkpoint without lr_step: its rate is the base, no step taken)"""
+        self.base = float(d["rate"])
+        self.s = int(d.get("lr_step", 0))
