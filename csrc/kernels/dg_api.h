@@ -309,7 +309,7 @@ hipError_t dg_augment_batch(uint8_t* planes, int* labels, int B, const uint8_t* 
 int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
                         unsigned long long board);
 
-// ------------------------------------------------- optim.hip (modules _dgopt and _dgadam)
+// ---------------------------------------- optim.hip (modules _dgopt, _dgadam and _dglamb)
 // SGD with momentum over the flat vector, one launch: gi = g * gscale; gw = gi + wd * p inside
 // a decay range, else gi; v = mu * v + gw; p -= lr * (nesterov ? gw + mu * v : v).  ranges: a
 // HOST array of n_ranges <= 20 rows {begin, end} (elements; sorted, disjoint, non-empty, begin
@@ -333,6 +333,25 @@ hipError_t dg_adamw(float* p, const float* g, float* m, float* v, size_t n, cons
                     void* rec, float beta1, float beta2, float eps, float wd,
                     const long long* ranges, int n_ranges, float gscale, const float* gate,
                     const void* g16, hipStream_t s);
+
+// LAMB over the flat vector (module _dglamb): Adam's m, v as dg_adamw; u = (c1 m) / (sqrt(v) c2
+// + eps), + wd p inside a range; per range k of the table SP = sum p^2, SU = sum u^2 (each
+// rounded to fp32), wn = sqrt(SP), un = sqrt(SU) (fp32), phi = fp32(double(wn) / double(un))
+// if both are finite and > 0, else 1; p -= (lr phi) u, phi = 1 outside every range.  Four
+// launches on s: dg_adamw_tick on rec (as dg_adamw), lamb_moments (m, v, u and per 1024-element
+// chunk and range meeting it one fp32 pair of partial sums), lamb_ratio (one workgroup per
+// range: the pairs summed in double, {wn, un, phi} to row k of tab), lamb_apply.  No atomics,
+// one fixed order: the same input gives the same bits on any grid.  u: n floats of scratch,
+// 16-byte aligned; part: part_n >= dg_lamb_partials(n, ranges, n_ranges) floats, 8-byte
+// aligned; tab: 20 x 3 floats.  dg_lamb_partials returns -1 for an invalid table or one with
+// more than 4 ranges meeting one chunk, which dg_lamb refuses too.  gate 0 leaves p, m, v, u,
+// rec, part and tab untouched.  Everything else as dg_adamw.
+long long dg_lamb_partials(size_t n, const long long* ranges, int n_ranges);
+hipError_t dg_lamb(float* p, const float* g, float* m, float* v, float* u, size_t n,
+                   const double* lr, void* rec, float* part, long long part_n, float* tab,
+                   float beta1, float beta2, float eps, float wd, const long long* ranges,
+                   int n_ranges, float gscale, const float* gate, const void* g16,
+                   hipStream_t s);
 
 // ---------------------------------------------------------------- clip.hip (module _dgclip)
 // Global-norm gradient clipping over the flat gradient: norm = |gscale| sqrt(sum g^2); r =

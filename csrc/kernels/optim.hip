@@ -1,7 +1,8 @@
 // The optimizers with a launch of their own over the flat fp32 master vector: SGD with momentum,
 // Nesterov and weight decay (dg_momentum: module _dgopt, opt_bindings.cpp, loaded only for
 // optimizer=momentum) and AdamW (dg_adamw, further down: module _dgadam, adam_bindings.cpp,
-// loaded only for optimizer=adamw).  Neither is part of _dghip, so its interface stays as
+// loaded only for optimizer=adamw) and LAMB (dg_lamb, last: module _dglamb, lamb_bindings.cpp,
+// loaded only for optimizer=lamb).  None is part of _dghip, so its interface stays as
 // recorded.  deep_go_amd/train/optim.py Momentum is the definition; per element i
 //
 //   gi = g[i] * gscale
@@ -242,6 +243,257 @@ adamw_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__
   }
 }
 
+// -------------------------------------------------------------------------------------- LAMB
+// Adam's update rescaled per conv-weight tensor by a trust ratio (deep_go_amd/train/optim.py
+// Lamb is the definition; module _dglamb, lamb_bindings.cpp, loaded only for optimizer=lamb).
+// The ranges R_k of the table are the adapted tensors; everything else takes ratio 1 and no
+// decay.  With the tick's t, c1, c2 as above, per applied step and element i
+//
+//   gi = g[i] * gscale
+//   m[i] = beta1 * m[i] + (1 - beta1) * gi
+//   v[i] = beta2 * v[i] + (1 - beta2) * gi * gi
+//   u[i] = (c1 * m[i]) / (sqrt(v[i]) * c2 + eps)  [+ wd * p[i]  if i lies in a range]
+//   per range k:  SP = sum p^2, SU = sum u^2 over R_k (each rounded to fp32), wn = sqrt(SP),
+//                 un = sqrt(SU) (fp32), phi = fp32(double(wn) / double(un)) if both are finite
+//                 and > 0, else 1
+//   p[i] = p[i] - (lr * phi_k) * u[i]                (phi = 1 outside every range)
+//
+// Four launches on the stream, no atomics, every sum in one fixed order that does not depend on
+// the grid:
+//
+//   adamw_tick    as for AdamW
+//   lamb_moments  adamw_kernel's shape; writes m, v and u, and per CHUNK (the CE elements of one
+//                 workgroup pass) and range meeting it one fp32 pair (sum p^2, sum u^2) over the
+//                 chunk's elements inside that range: thread chains in element order, the
+//                 wave's xor butterfly, (w0 + w1) + (w2 + w3) — gradnorm_partial's order
+//                 (clip.hip).  The pair of chunk c's j-th range (j counts from the first range
+//                 that has not ended before the chunk) sits at part[(c LAMB_SLOTS + j) 2]; the
+//                 n % 4 tail, which lies in at most one range because ranges begin on multiples
+//                 of RANGE_ALIGN, has the chunk after the last to itself
+//   lamb_ratio    one workgroup per range: its pairs summed in double (thread t takes the
+//                 range's chunks t, t + MT, ... in order, then the same trees, then the tail's
+//                 pair), {wn, un, phi} to row k of the record table
+//   lamb_apply    p -= (lr phi) u with the chunk's ratios found by the same scalar lookup
+//
+// Stream order separates them: no thread reads what a thread of its own launch writes.  Each
+// returns behind a closed gate before any access.
+constexpr int LAMB_SLOTS = 4;     // ranges that may meet one chunk (the launcher checks)
+constexpr int LAMB_ROW = 3;       // floats per row of the record table: wn, un, phi
+
+// how many ranges end at or before element e0: the first that can meet a chunk beginning there
+DG_DEV int ranges_before(const DecayRanges& R, unsigned e0) {
+  int r = 0;
+#pragma unroll
+  for (int q = 0; q < MAX_RANGES; ++q) r += R.e[q] <= e0 ? 1 : 0;
+  return r;
+}
+
+// the chunk [e0, e1) of 4-vector c0 in elements, saturated as in chunk_mask
+DG_DEV void chunk_bounds(size_t c0, unsigned& e0, unsigned& e1) {
+  const size_t c4 = c0 * 4;
+  e0 = c4 < NO_RANGE ? (unsigned)c4 : NO_RANGE;
+  e1 = c4 + CE < NO_RANGE ? (unsigned)(c4 + CE) : NO_RANGE;
+}
+
+// range q clipped to the chunk, in elements from the chunk's first
+DG_DEV void chunk_span(const DecayRanges& R, int q, unsigned e0, unsigned e1, int& lo, int& hi) {
+  lo = R.b[q] > e0 ? (int)(R.b[q] - e0) : 0;
+  hi = R.e[q] < e1 ? (int)(R.e[q] - e0) : CE;
+}
+
+DG_DEV double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// one element: m, v as adamw_update; -> u without the decay term
+DG_DEV float lamb_update(float& m, float& v, float g, float c1, float b1, float o1, float b2,
+                         float o2, float c2, float eps, float gscale) {
+  const float gi = g * gscale;
+  m = b1 * m + o1 * gi;
+  v = b2 * v + (o2 * gi) * gi;
+  return (c1 * m) / (sqrtf(v) * c2 + eps);
+}
+
+template <typename G>
+__global__ void __launch_bounds__(MT)
+lamb_moments(const float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m,
+             float* __restrict__ v, float* __restrict__ u, size_t n,
+             const AdamRecord* __restrict__ rec, float b1, float o1, float b2, float o2,
+             float eps, float wd, const DecayRanges R, float gscale, float* __restrict__ part,
+             const float* __restrict__ gate) {
+  // gate 0 skips the update: return before any access
+  if (gate && *gate == 0.f) return;
+  __shared__ float s_w[2][MT / 64];
+  const float c1 = rec->c1, c2 = rec->c2;
+  const size_t n4 = n / 4;
+  const int tid = threadIdx.x;
+  for (size_t c0 = blockIdx.x * (size_t)MT; c0 < n4; c0 += (size_t)gridDim.x * MT) {
+    const size_t i = c0 + tid;
+    const bool live = i < n4;
+    f32x4 pv = {0.f, 0.f, 0.f, 0.f}, uv = {0.f, 0.f, 0.f, 0.f}, mv, vv;
+    decltype(grad4_raw(g, 0)) gv;
+    if (live) {
+      pv = ((const f32x4*)p)[i];
+      mv = ((const f32x4*)m)[i];
+      vv = ((const f32x4*)v)[i];
+      gv = grad4_raw(g, i);
+    }
+    const f32x4 w = chunk_mask(R, c0, tid, wd);
+    if (live) {
+      const f32x4 gf = grad4_f32(gv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float mj = mv[j], vj = vv[j];
+        uv[j] = lamb_update(mj, vj, gf[j], c1, b1, o1, b2, o2, c2, eps, gscale) + w[j] * pv[j];
+        mv[j] = mj, vv[j] = vj;
+      }
+      ((f32x4*)m)[i] = mv;
+      ((f32x4*)v)[i] = vv;
+      ((f32x4*)u)[i] = uv;
+    }
+    // the chunk's pairs: uniform over the workgroup (almost always one range, often none)
+    unsigned e0, e1;
+    chunk_bounds(c0, e0, e1);
+    const size_t slot0 = c0 / MT * LAMB_SLOTS;
+    int q = ranges_before(R, e0);
+    for (int j = 0; j < LAMB_SLOTS && q < MAX_RANGES && R.b[q] < e1; ++j, ++q) {
+      int lo, hi;
+      chunk_span(R, q, e0, e1, lo, hi);
+      float sp = 0.f, su = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (live && tid * 4 + k >= lo && tid * 4 + k < hi) {
+          sp += pv[k] * pv[k];
+          su += uv[k] * uv[k];
+        }
+      sp = wave_sum(sp);
+      su = wave_sum(su);
+      if ((tid & 63) == 0) s_w[0][tid >> 6] = sp, s_w[1][tid >> 6] = su;
+      __syncthreads();
+      if (tid == 0)
+        ((float2*)part)[slot0 + j] = float2{(s_w[0][0] + s_w[0][1]) + (s_w[0][2] + s_w[0][3]),
+                                            (s_w[1][0] + s_w[1][1]) + (s_w[1][2] + s_w[1][3])};
+      __syncthreads();
+    }
+  }
+  // the n % 4 tail: at most three elements, all on one lane, in order; their pair goes to the
+  // chunk after the last
+  if (blockIdx.x == 0 && tid == 0 && n4 * 4 < n) {
+    float sp = 0.f, su = 0.f;
+    bool any = false;
+    for (size_t i = n4 * 4; i < n; ++i) {
+      const float in = tail_mask(R, i, 1.f);
+      const float pi = p[i];
+      float mi = m[i], vi = v[i];
+      const float ui =
+          lamb_update(mi, vi, grad_at(g, i), c1, b1, o1, b2, o2, c2, eps, gscale) +
+          (in * wd) * pi;
+      m[i] = mi;
+      v[i] = vi;
+      u[i] = ui;
+      if (in != 0.f) {
+        any = true;
+        sp += pi * pi;
+        su += ui * ui;
+      }
+    }
+    if (any) ((float2*)part)[(n4 + MT - 1) / MT * LAMB_SLOTS] = float2{sp, su};
+  }
+}
+
+// workgroup k: range k's pairs -> {wn, un, phi}
+__global__ void __launch_bounds__(MT)
+lamb_ratio(const float* __restrict__ part, size_t n, const DecayRanges R,
+           float* __restrict__ tab, const float* __restrict__ gate) {
+  // gate 0 skips the update: return before any access
+  if (gate && *gate == 0.f) return;
+  __shared__ double s_w[2][MT / 64];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  const size_t n4 = n / 4;
+  const size_t b = R.b[k], e = R.e[k];
+  const size_t lim = e < n4 * 4 ? e : n4 * 4;     // (the tail's elements are not in a chunk)
+  double sp = 0.0, su = 0.0;
+  if (b < lim) {
+    const size_t last = (lim - 1) / CE;
+    for (size_t c = b / CE + tid; c <= last; c += MT) {
+      // the range's slot in chunk c: the ranges in front of it that reach into the chunk
+      int j = 0;
+      for (int q = 0; q < k; ++q) j += R.e[q] > c * CE ? 1 : 0;
+      const float2 pr = ((const float2*)part)[c * LAMB_SLOTS + j];
+      sp += (double)pr.x;
+      su += (double)pr.y;
+    }
+  }
+  sp = wave_sum_d(sp);
+  su = wave_sum_d(su);
+  if ((tid & 63) == 0) s_w[0][tid >> 6] = sp, s_w[1][tid >> 6] = su;
+  __syncthreads();
+  if (tid != 0) return;
+  sp = (s_w[0][0] + s_w[0][1]) + (s_w[0][2] + s_w[0][3]);
+  su = (s_w[1][0] + s_w[1][1]) + (s_w[1][2] + s_w[1][3]);
+  if (e > n4 * 4) {
+    const float2 pr = ((const float2*)part)[(n4 + MT - 1) / MT * LAMB_SLOTS];
+    sp += (double)pr.x;
+    su += (double)pr.y;
+  }
+  // the sums rounded to fp32 (above its range: inf), the roots rounded to fp32, the ratio from
+  // those fp32 norms in double
+  const float wn = (float)sqrt((double)(float)sp), un = (float)sqrt((double)(float)su);
+  const bool ok = wn > 0.f && un > 0.f && wn <= 3.402823466e38f && un <= 3.402823466e38f;
+  tab[k * LAMB_ROW + 0] = wn;
+  tab[k * LAMB_ROW + 1] = un;
+  tab[k * LAMB_ROW + 2] = ok ? (float)((double)wn / (double)un) : 1.f;
+}
+
+// the ratios of thread tid's four elements in the chunk of 4-vector c0: chunk_mask's lookup
+// with a value per range, 1 outside every range
+DG_DEV f32x4 chunk_ratio(const DecayRanges& R, size_t c0, int tid, const float* tab) {
+  unsigned e0, e1;
+  chunk_bounds(c0, e0, e1);
+  f32x4 f = {1.f, 1.f, 1.f, 1.f};
+  for (int q = ranges_before(R, e0); q < MAX_RANGES && R.b[q] < e1; ++q) {
+    int lo, hi;
+    chunk_span(R, q, e0, e1, lo, hi);
+    const float phi = tab[q * LAMB_ROW + 2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (tid * 4 + j >= lo && tid * 4 + j < hi) f[j] = phi;
+  }
+  return f;
+}
+
+__global__ void __launch_bounds__(MT)
+lamb_apply(float* __restrict__ p, const float* __restrict__ u, size_t n,
+           const double* __restrict__ lr, const float* __restrict__ tab, const DecayRanges R,
+           const float* __restrict__ gate) {
+  // gate 0 skips the update: return before any access
+  if (gate && *gate == 0.f) return;
+  const float l = (float)(*lr);
+  const size_t n4 = n / 4;
+  const int tid = threadIdx.x;
+  for (size_t c0 = blockIdx.x * (size_t)MT; c0 < n4; c0 += (size_t)gridDim.x * MT) {
+    const size_t i = c0 + tid;
+    const bool live = i < n4;
+    f32x4 pv, uv;
+    if (live) {
+      pv = ((const f32x4*)p)[i];
+      uv = ((const f32x4*)u)[i];
+    }
+    const f32x4 f = chunk_ratio(R, c0, tid, tab);
+    if (live) ((f32x4*)p)[i] = pv - (l * f) * uv;
+  }
+  // the n % 4 tail: at most three elements, one lane each
+  const size_t i = n4 * 4 + tid;
+  if (blockIdx.x == 0 && i < n) {
+    float phi = 1.f;
+    for (int q = 0; q < MAX_RANGES; ++q)
+      if (i >= R.b[q] && i < R.e[q]) phi = tab[q * LAMB_ROW + 2];
+    p[i] = p[i] - (l * phi) * u[i];
+  }
+}
+
 }  // namespace
 
 // the host table {begin, end} x n_ranges -> R, or false: more than MAX_RANGES rows, a count
@@ -329,6 +581,63 @@ hipError_t dg_adamw(float* p, const float* g, float* m, float* v, size_t n, cons
   else
     hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(MT), 0, s, p, g, m, v, n, lr, r,
                        beta1, o1, beta2, o2, eps, wd, R, gscale, gate);
+  return hipGetLastError();
+}
+
+// the floats of LAMB's partial buffer for n elements: LAMB_SLOTS pairs per chunk and the tail's
+// chunk; -1: an invalid table, or one with more than LAMB_SLOTS ranges meeting one chunk
+long long dg_lamb_partials(size_t n, const long long* ranges, int n_ranges) {
+  DecayRanges R;
+  if (!decay_ranges(ranges, n_ranges, n, R)) return -1;
+  // a chunk that several ranges meet holds the begin of one of them
+  for (int k = 0; k < n_ranges; ++k) {
+    const unsigned long long c = R.b[k] / CE;
+    int meet = 0;
+    for (int q = 0; q < n_ranges; ++q)
+      meet += (R.b[q] < (c + 1) * CE && R.e[q] > c * CE) ? 1 : 0;
+    if (meet > LAMB_SLOTS) return -1;
+  }
+  const size_t chunks = (n / 4 + MT - 1) / MT;
+  return (long long)((chunks + 1) * LAMB_SLOTS * 2);
+}
+
+hipError_t dg_lamb(float* p, const float* g, float* m, float* v, float* u, size_t n,
+                   const double* lr, void* rec, float* part, long long part_n, float* tab,
+                   float beta1, float beta2, float eps, float wd, const long long* ranges,
+                   int n_ranges, float gscale, const float* gate, const void* g16,
+                   hipStream_t s) {
+  DecayRanges R;
+  if (!decay_ranges(ranges, n_ranges, n, R)) return hipErrorInvalidValue;
+  const long long need = dg_lamb_partials(n, ranges, n_ranges);
+  // (written so that a NaN is refused too)
+  if (need < 0 || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) ||
+      !(eps > 0.f))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!p || !m || !v || !u || !lr || !rec || !part || !tab || !(g || g16))
+    return hipErrorInvalidValue;
+  // the 16-byte (bf16: 8-byte) vector accesses; the record's int64; the partials' pairs
+  if ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)u | (uintptr_t)g) & 15) ||
+      ((uintptr_t)g16 & 7) || ((uintptr_t)rec & 7) || ((uintptr_t)part & 7) ||
+      ((uintptr_t)tab & 3) || part_n < need)
+    return hipErrorInvalidValue;
+  const AdamRecord* r = (const AdamRecord*)rec;
+  if (hipError_t e = dg_adamw_tick(rec, beta1, beta2, gate, s)) return e;
+  const unsigned blocks = grid_blocks(n);
+  const float o1 = 1.f - beta1, o2 = 1.f - beta2;
+  if (g16)
+    hipLaunchKernelGGL(lamb_moments<bf16_t>, dim3(blocks), dim3(MT), 0, s, p,
+                       (const bf16_t*)g16, m, v, u, n, r, beta1, o1, beta2, o2, eps, wd, R,
+                       gscale, part, gate);
+  else
+    hipLaunchKernelGGL(lamb_moments<float>, dim3(blocks), dim3(MT), 0, s, p, g, m, v, u, n, r,
+                       beta1, o1, beta2, o2, eps, wd, R, gscale, part, gate);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (n_ranges > 0) {
+    hipLaunchKernelGGL(lamb_ratio, dim3(n_ranges), dim3(MT), 0, s, part, n, R, tab, gate);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  hipLaunchKernelGGL(lamb_apply, dim3(blocks), dim3(MT), 0, s, p, u, n, lr, tab, R, gate);
   return hipGetLastError();
 }
 

@@ -5,13 +5,15 @@ Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
 ``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise),
 ``deep_go_amd/_native/_dgadam<EXT>`` (the AdamW optimizer's kernels: the same optim.hip behind
 bindings of its own),
+``deep_go_amd/_native/_dglamb<EXT>`` (the LAMB optimizer's kernels: optim.hip again),
 ``deep_go_amd/_native/_dgclip<EXT>`` (gradient clipping by the global norm: clip.hip),
 ``deep_go_amd/_native/_dgema<EXT>`` (the moving average of the weights: ema.hip),
 ``deep_go_amd/_native/_dgsched<EXT>`` (the learning-rate schedule: sched.hip) and
 ``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
 pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
 
-Usage: ``python -m deep_go_amd._build [--force] [--only hip|aug|opt|adam|clip|ema|sched|cpu|comm]
+Usage: ``python -m deep_go_amd._build [--force] [--only
+hip|aug|opt|adam|lamb|clip|ema|sched|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -130,6 +132,13 @@ def build_adam(force: bool = False) -> Path:
     return _build_small("adam", "optim.hip", "adam_bindings.cpp", force)
 
 
+def build_lamb(force: bool = False) -> Path:
+    """_dglamb: LAMB (optim.hip, where it shares the range table, the chunk lookup, the gradient
+    loads and the count's launch with AdamW, + lamb_bindings.cpp).  A module of its own: the
+    public names of _dgopt and _dgadam are pinned by their tests."""
+    return _build_small("lamb", "optim.hip", "lamb_bindings.cpp", force)
+
+
 def build_clip(force: bool = False) -> Path:
     """_dgclip: global-norm gradient clipping (clip.hip + clip_bindings.cpp), imported only for
     grad_clip > 0 and apart from the other modules, whose interfaces are recorded or pinned."""
@@ -203,6 +212,7 @@ def build_all(force: bool = False) -> None:
     build_aug(force)
     build_opt(force)
     build_adam(force)
+    build_lamb(force)
     build_clip(force)
     build_ema(force)
     build_sched(force)
@@ -212,8 +222,8 @@ def build_all(force: bool = False) -> None:
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "clip", "ema", "sched", "cpu",
-                                       "comm"])
+    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "lamb", "clip", "ema", "sched",
+                                       "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
@@ -227,6 +237,8 @@ def main(argv=None):
         print(build_opt(a.force))
     if a.only in (None, "adam") and not a.sanitize:
         print(build_adam(a.force))
+    if a.only in (None, "lamb") and not a.sanitize:
+        print(build_lamb(a.force))
     if a.only in (None, "clip") and not a.sanitize:
         print(build_clip(a.force))
     if a.only in (None, "ema") and not a.sanitize:

@@ -1,7 +1,10 @@
 """Command line: ``python -m deep_go_amd <command> ...``
 
   train     [--preset NAME] [key=value ...] --iters N [--export-t7 PATH] [--auto-resume]
-            (localtest.lua / default-experiment.lua / notebook equivalents via presets)
+            (localtest.lua / default-experiment.lua / notebook equivalents via presets;
+            optimizer=sgd|rmsprop|momentum|adamw|lamb — lamb takes adamw's fields adam_beta1,
+            adam_beta2, adam_eps, weight_decay and logs one kind="lamb" record of the per-layer
+            trust ratios on logging iterations)
   resume    CKPT --iters N [--reset-optimizer] [--id NAME] [key=value ...]
             (experiments/repeated.lua: -gpu/-num/-iters -> --device/--id/--iters)
   eval      CKPT [--split test] [--n N] [--symmetries 8] [--top K] [--ema]

@@ -11,11 +11,12 @@ Parity notes (reference = Torch7 ``vipmath/deep-go``):
   experiments.  Here the layer schedule is derived, never mutated.
 * Unknown override keys are rejected (the reference silently ignored the typo
   ``validation_size`` in ``localtest.lua:8``).
-* ``optimizer`` has two additions to the reference's sgd | rmsprop: ``momentum`` (fields
-  ``momentum``, ``nesterov``, ``weight_decay``) and ``adamw`` (``adam_beta1``, ``adam_beta2``,
-  ``adam_eps``, ``weight_decay``).  ``override`` checks their ranges and rejects a field set
+* ``optimizer`` has three additions to the reference's sgd | rmsprop: ``momentum`` (fields
+  ``momentum``, ``nesterov``, ``weight_decay``), ``adamw`` (``adam_beta1``, ``adam_beta2``,
+  ``adam_eps``, ``weight_decay``) and ``lamb`` (adamw's fields and state: Adam's update rescaled
+  per conv-weight tensor by ||w|| / ||update||, train/optim.py Lamb).  ``override`` checks their ranges and rejects a field set
   without the optimizer it belongs to; checkpoints from before a field existed load its default.
-* ``grad_clip`` (an addition; 0 = off) caps the gradient's global L2 norm before any of the four
+* ``grad_clip`` (an addition; 0 = off) caps the gradient's global L2 norm before any of the
   optimizers reads it: with c = grad_clip, norm = |gscale| * ||g||_2, scale = min(1, c / (norm +
   1e-6)), g *= scale — ``torch.nn.utils.clip_grad_norm_`` (train/optim.py clip_grad_).  Once per
   APPLIED step: a skipped step clips nothing.  ``override`` refuses a negative or non-finite value.
@@ -76,13 +77,15 @@ class ExperimentConfig:
     # sgd | rmsprop (the reference's misnamed AdagradOptimizer) | momentum (SGD with momentum,
     # train/optim.py Momentum: momentum, nesterov, weight_decay) | adamw (Adam with decoupled
     # weight decay, train/optim.py AdamW: adam_beta1, adam_beta2, adam_eps, weight_decay; with
-    # weight_decay=0 it is Adam).  A field set without its optimizer is rejected, not ignored
+    # weight_decay=0 it is Adam) | lamb (layer-wise trust ratios on Adam, train/optim.py Lamb:
+    # adamw's fields).  A field set without its optimizer is rejected, not ignored
     optimizer: str = "sgd"
     rmsprop_decay: float = 0.9
     momentum: float = 0.9          # velocity decay mu, in [0, 1)
     nesterov: bool = False         # step along gw + mu v instead of v
     # on the conv weights only (never on the biases): momentum's L2 coefficient (added to the
-    # gradient), adamw's decoupled decay (p *= 1 - rate * weight_decay)
+    # gradient), adamw's decoupled decay (p *= 1 - rate * weight_decay), lamb's decay term (added
+    # to the update before its norm is taken)
     weight_decay: float = 0.0
     adam_beta1: float = 0.9        # first-moment decay, in [0, 1)
     adam_beta2: float = 0.999      # second-moment decay, in [0, 1)
@@ -222,7 +225,7 @@ def _coerce(name: str, value: Any, current: Any) -> Any:
 
 
 _CHOICES = {"nan_policy": ("guard", "skip", "raise"), "comm": ("auto", "native", "torch"),
-            "optimizer": ("sgd", "rmsprop", "momentum", "adamw"), "grad_dtype": ("fp32", "bf16"),
+            "optimizer": ("sgd", "rmsprop", "momentum", "adamw", "lamb"), "grad_dtype": ("fp32", "bf16"),
             "sampling": ("game", "position"), "augment": ("none", "d4"),
             "lr_schedule": ("none", "constant", "linear", "cosine", "step")}
 # (LR_KINDS below: the same names without none)
@@ -255,14 +258,15 @@ def override(cfg: ExperimentConfig, kw: Dict[str, Any]) -> ExperimentConfig:
     # (the other update paths have no such terms: do not ignore a setting silently)
     if new.optimizer != "momentum" and new.nesterov:
         raise ValueError(f"nesterov needs optimizer=momentum, not optimizer={new.optimizer!r}")
-    if new.optimizer not in ("momentum", "adamw") and new.weight_decay != 0.0:
-        raise ValueError(f"weight_decay needs optimizer=momentum or adamw, "
+    if new.optimizer not in ("momentum", "adamw", "lamb") and new.weight_decay != 0.0:
+        raise ValueError(f"weight_decay needs optimizer=momentum or adamw or lamb, "
                          f"not optimizer={new.optimizer!r}")
-    if new.optimizer != "adamw":
+    if new.optimizer not in ("adamw", "lamb"):
         base = ExperimentConfig()
         for k in ("adam_beta1", "adam_beta2", "adam_eps"):
             if getattr(new, k) != getattr(base, k):
-                raise ValueError(f"{k} needs optimizer=adamw, not optimizer={new.optimizer!r}")
+                raise ValueError(f"{k} needs optimizer=adamw or lamb, "
+                                 f"not optimizer={new.optimizer!r}")
     _check_lr_schedule(new)
     return new
 

@@ -31,7 +31,7 @@ import torch
 from ..config import LR_KINDS, NUM_POINTS, ExperimentConfig
 from ..data.batch import pack_batch, packed_batch_bytes, unpack_views  # noqa: F401
 from ..ops import layouts as LY
-from ..ops.native import adam, clip, ema, hip, opt, sched, stream_handle
+from ..ops.native import adam, clip, ema, hip, lamb, opt, sched, stream_handle
 from ..utils import streamcheck, trace
 from .gocnn import ParamLayout, init_params
 
@@ -256,6 +256,28 @@ class HipGoNet:
             # module's code object is loaded here, not inside the capture of a step graph
             self._adamw(self._opt.adamw, self.grads.data_ptr(), 1.0,
                         torch.zeros(1, device=dev).data_ptr(), stream_handle())
+        # optimizer=lamb: Adam's state under the same attributes (and checkpoint keys), the
+        # update u as a scratch vector, the per-chunk partial sums of squares, the table of
+        # 20 x {wn, un, phi} of the last applied step, and the kernels' module (_dglamb:
+        # optim.hip)
+        self.lamb_u = self.lamb_part = self.lamb_rec = None
+        if cfg.optimizer == "lamb":
+            self.adam_m = torch.zeros_like(self.params)
+            self.adam_v = torch.zeros_like(self.params)
+            self.adam_t = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._opt = lamb()
+            self._wd_ranges = np.ascontiguousarray(
+                np.array(self.layout.weight_ranges(), dtype=np.int64))
+            r = self._wd_ranges
+            self.lamb_u = torch.zeros_like(self.params)
+            self.lamb_part = torch.zeros(
+                self._opt.lamb_partials(self.params.numel(), r.ctypes.data, len(r)),
+                dtype=torch.float32, device=dev)
+            self.lamb_rec = torch.zeros(20 * 3, dtype=torch.float32, device=dev)
+            # all four launches behind a closed gate (they return at once and t stays 0): the
+            # module's code object is loaded here, not inside the capture of a step graph
+            self._lamb(self._opt.lamb, self.grads.data_ptr(), 1.0,
+                       torch.zeros(1, device=dev).data_ptr(), stream_handle())
         # grad_clip > 0: the partials of the gradient's sum of squares, the 16-byte record
         # {float norm; float scale; int64 clipped} (two int64: the first holds norm, scale) and
         # the kernels' module (_dgclip: clip.hip).  The clip scans the reduced gradient, so
@@ -1471,8 +1493,8 @@ class HipGoNet:
         needs the reduced gradient; the bf16 wire twin is a DP format), no gradient hooks, and
         every layer's slabs / partials in buffers of their own: one grouped weight-gradient
         launch, plus at most the first layer's own chain.  DG_FUSED_UPDATE=0: never (and the
-        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum | adamw, or
-        grad_clip > 0 with any optimizer: never (their update is a launch of its own behind the
+        optimizer keeps the separate SGD + refresh launches).  optimizer=momentum | adamw | lamb,
+        or grad_clip > 0 with any optimizer: never (their update is a launch of its own behind the
         reduced gradient, not part of grad_update)."""
         if not self.knobs.FUSED_UPDATE or self._own_update:
             return False
@@ -1544,8 +1566,9 @@ class HipGoNet:
         """The update: [finite gate] -> [fp8 scale update] -> ONE fused launch (grad_update:
         the gradient's pass 2 when the step deferred it, SGD / RMSProp on every parameter,
         the operand copies the next step reads, LR decay).  DG_FUSED_UPDATE=0: the separate
-        SGD / RMSProp and weight-refresh launches.  optimizer=momentum | adamw: their own
-        launch(es) in the place of the SGD launch, then the weight refresh and LR decay.
+        SGD / RMSProp and weight-refresh launches.  optimizer=momentum | adamw | lamb: their
+        own launch(es) in the place of the SGD launch (lamb: four — the count, the moments and
+        partial sums, the ratios, the update), then the weight refresh and LR decay.
         grad_clip > 0: the clip's two launches in front of the optimizer's, which is then a
         separate launch for sgd | rmsprop too and reads the fp32 gradient.  ema_decay > 0: the
         average's two launches behind the last launch that writes the parameters, on either
@@ -1581,7 +1604,10 @@ class HipGoNet:
             self._grad_clip(grad_scale, gate, s)
             w16, g = False, self.grads.data_ptr()
         if not self.knobs.FUSED_UPDATE or self._own_update:
-            if self.adam_m is not None:
+            if self.lamb_u is not None:
+                self._lamb(self._opt.lamb_bf16 if w16 else self._opt.lamb, g, grad_scale,
+                           gate, s)
+            elif self.adam_m is not None:
                 self._adamw(self._opt.adamw_bf16 if w16 else self._opt.adamw, g, grad_scale,
                             gate, s)
             elif self.vel is not None:
@@ -1630,6 +1656,24 @@ class HipGoNet:
            self.layout.numel, self.lr.data_ptr(), self.adam_t.data_ptr(), float(c.adam_beta1),
            float(c.adam_beta2), float(c.adam_eps), float(c.weight_decay), r.ctypes.data, len(r),
            grad_scale, gate, s)
+
+    def _lamb(self, fn, g, grad_scale, gate, s):
+        """optimizer=lamb's four launches (the count's, the moments and partial sums, the
+        ratios, the update): optim.hip."""
+        r, c = self._wd_ranges, self.cfg
+        fn(self.params.data_ptr(), g, self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+           self.lamb_u.data_ptr(), self.layout.numel, self.lr.data_ptr(),
+           self.adam_t.data_ptr(), self.lamb_part.data_ptr(), self.lamb_part.numel(),
+           self.lamb_rec.data_ptr(), float(c.adam_beta1), float(c.adam_beta2),
+           float(c.adam_eps), float(c.weight_decay), r.ctypes.data, len(r), grad_scale, gate, s)
+
+    def lamb_stats(self):
+        """optimizer=lamb: per conv-weight tensor (wn, un, phi) of the last applied step, from
+        the device table.  Syncs."""
+        if self.lamb_rec is None:
+            raise RuntimeError("no trust ratios: optimizer is not lamb")
+        rows = self.lamb_rec.cpu().view(20, 3)[:len(self._wd_ranges)].tolist()
+        return [tuple(r) for r in rows]
 
     def _grad_clip(self, grad_scale, gate, s):
         """grad_clip's two launches (the partial sums of squares, then the scale): clip.hip."""

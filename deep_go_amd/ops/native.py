@@ -3,7 +3,8 @@
 ``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
 (the batch-augmentation kernel), imported only when augmentation is asked for; ``opt()`` the
 ``_dgopt`` module (the momentum optimizer's kernel), imported only for it; ``adam()`` the
-``_dgadam`` module (the AdamW optimizer's kernels), likewise; ``clip()`` the ``_dgclip`` module
+``_dgadam`` module (the AdamW optimizer's kernels), likewise; ``lamb()`` the ``_dglamb`` module
+(the LAMB optimizer's kernels), likewise; ``clip()`` the ``_dgclip`` module
 (gradient clipping by the global norm), imported only for ``grad_clip > 0``; ``ema()`` the
 ``_dgema`` module (the moving average of the weights), imported only for ``ema_decay > 0``;
 ``sched()`` the ``_dgsched`` module (the learning-rate schedule's launch), imported only for
@@ -42,6 +43,7 @@ def _load(name: str):
             from .. import _build
             {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
              "_dgopt": _build.build_opt, "_dgadam": _build.build_adam,
+             "_dglamb": _build.build_lamb,
              "_dgclip": _build.build_clip, "_dgema": _build.build_ema,
              "_dgsched": _build.build_sched,
              "_dgcomm": _build.build_comm}.get(
@@ -72,6 +74,11 @@ def opt():
 def adam():
     """_dgadam: AdamW, Adam with decoupled weight decay (csrc/kernels/optim.hip)."""
     return _load("_dgadam")
+
+
+def lamb():
+    """_dglamb: LAMB, layer-wise trust ratios on Adam (csrc/kernels/optim.hip)."""
+    return _load("_dglamb")
 
 
 def clip():

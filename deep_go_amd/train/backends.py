@@ -3,11 +3,13 @@
 Both expose the same small surface used by the training loop:
   set_batch(planes uint8 [B,9,19,19], player, rank, labels)   (host numpy or tensors)
   forward_backward()         loss/argmax of the batch + gradients (global-batch mean)
-  optimizer_step()           SGD/RMSProp/Momentum/AdamW + per-step LR decay
+  optimizer_step()           SGD/RMSProp/Momentum/AdamW/LAMB + per-step LR decay
   evaluate(n)                forward only on the first n boards of the current batch
   loss_sum() / correct()     of the last forward (host floats; synchronising)
   clip_stats()               grad_clip > 0: (grad_norm, clip_scale, clipped_steps) of the last
                              applied step and of the run (synchronising)
+  lamb_stats()               optimizer=lamb: per conv-weight tensor (||w||, ||update||, trust
+                             ratio) of the last applied step (synchronising)
   ema_params() / ema_steps() ema_decay > 0: the moving average of the weights (on the host) and
                              the count of averaging steps applied
   ema_weights()              ema_decay > 0: a context manager inside which evaluate() runs on
@@ -46,7 +48,7 @@ from ..config import ExperimentConfig
 from ..models.gocnn import ParamLayout, init_params, reference_forward
 from ..ops.native import cpu
 from ..parallel import dp
-from .optim import SGD, AdamW, LRSchedule, Momentum, RMSProp, WeightEMA, clip_grad_
+from .optim import SGD, AdamW, Lamb, LRSchedule, Momentum, RMSProp, WeightEMA, clip_grad_
 
 
 def _np(x, dtype):
@@ -88,6 +90,10 @@ class CPUBackend:
             self.opt = AdamW(cfg.rate, cfg.rateDecay, cfg.adam_beta1, cfg.adam_beta2,
                              cfg.adam_eps, cfg.weight_decay, self.layout.numel,
                              self.layout.weight_ranges())
+        elif cfg.optimizer == "lamb":
+            self.opt = Lamb(cfg.rate, cfg.rateDecay, cfg.adam_beta1, cfg.adam_beta2,
+                            cfg.adam_eps, cfg.weight_decay, self.layout.numel,
+                            self.layout.weight_ranges())
         else:
             self.opt = SGD(cfg.rate, cfg.rateDecay)
         # lr_schedule != none: base and s live here; the optimizer's rate is rewritten from them
@@ -228,6 +234,12 @@ class CPUBackend:
         """grad_clip > 0: (grad_norm, clip_scale) of the last applied step and the number of
         applied steps that clipped so far."""
         return self._clip
+
+    def lamb_stats(self):
+        """optimizer=lamb: per conv-weight tensor (wn, un, phi) of the last applied step."""
+        if not isinstance(self.opt, Lamb):
+            raise RuntimeError("no trust ratios: optimizer is not lamb")
+        return self.opt.lamb_stats()
 
     def _need_ema(self):
         if self.ema is None:
@@ -420,6 +432,11 @@ class HIPBackend:
         """grad_clip > 0: (grad_norm, clip_scale) of the last applied step and the number of
         applied steps that clipped so far, from the device record (syncs)."""
         return self.net.clip_stats()
+
+    def lamb_stats(self):
+        """optimizer=lamb: per conv-weight tensor (wn, un, phi) of the last applied step, from
+        the device table (syncs)."""
+        return self.net.lamb_stats()
 
     def ema_params(self) -> torch.Tensor:
         """ema_decay > 0: the moving average of the weights, on the host (syncs)."""

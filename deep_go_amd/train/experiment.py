@@ -295,6 +295,11 @@ class Experiment:
                     gn, cs, nclip = be.clip_stats()
                     self.metrics.record(kind="clip", step=step, grad_norm=gn, clip_scale=cs,
                                         clipped_steps=nclip)
+                if cfg.optimizer == "lamb" and step % cfg.log_interval == 0:
+                    # (after the update: the trust ratios of the last applied step, per layer)
+                    phi = [s[2] for s in be.lamb_stats()]
+                    self.metrics.record(kind="lamb", step=step, phi=phi, phi_min=min(phi),
+                                        phi_max=max(phi))
                 if cfg.lr_schedule != "none" and step % cfg.log_interval == 0:
                     # (after the update: the schedule's state as the next step finds it, rate =
                     # base_rate * factor(lr_step))

@@ -1,6 +1,6 @@
 """Optimizers over the flat parameter vector (CPU path; the GPU path runs the same math in
 ``sgd_kernel`` / ``rmsprop_kernel``, csrc/kernels/elementwise.hip, and ``momentum_kernel`` /
-``adamw_kernel``, csrc/kernels/optim.hip).
+``adamw_kernel`` / ``lamb_moments``, ``lamb_ratio``, ``lamb_apply``, csrc/kernels/optim.hip).
 
 * ``SGD`` (optimizer.lua:16-27): theta -= rate * g, then rate *= (1 - decay) — so after t
   steps rate_t = rate_0 * (1 - decay)^t.  The rate is a Python float (double), as in Lua.
@@ -21,6 +21,17 @@
   A skipped step (a non-finite loss or gradient) is no call of ``step``: m, v and t stay, only
   the rate decays, so t falls behind the trainer's iteration count.  beta1, beta2, eps are
   taken as their fp32 values, as the kernel receives them.
+* ``Lamb`` (an addition): Adam's update rescaled per conv-weight tensor by a trust ratio.  The
+  adapted tensors are the ranges R_k of ``ParamLayout.weight_ranges()``; the biases and the
+  padding take ratio 1 and no decay (apex's default for tensors without weight decay).  t, c1,
+  c2, m, v as ``AdamW``; r = (c1 m) / (sqrt(v) c2 + eps); u = r + weight_decay theta inside a
+  range, r elsewhere; per range SP = sum theta^2, SU = sum u^2 (accumulated in double from the
+  fp32 values, each rounded to fp32), wn = fp32(sqrt(SP)), un = fp32(sqrt(SU)), phi =
+  fp32(double(wn) / double(un)) if both are finite and > 0, else 1 (no clamp; an overflowing
+  sum is inf and gives 1); theta -= (rate phi) u; then rate *= (1 - decay).  A skipped step is
+  no call of ``step``, as for ``AdamW``.  The state is Adam's and is saved under the same keys
+  (``adam_m``, ``adam_v``, ``adam_t``): a checkpoint moves between ``adamw`` and ``lamb`` with
+  its moments.
 
 ``clip_grad_`` (an addition; ``grad_clip`` > 0) runs before any of them, once per applied step:
 norm = |gscale| * sqrt(sum g^2), scale = min(1, c / (norm + 1e-6)), g *= scale, which is
@@ -171,6 +182,73 @@ class AdamW:
 
     def state_dict(self):
         return {"kind": "adamw", "rate": self.rate, "rate_decay": self.rate_decay,
+                "adam_m": self.m, "adam_v": self.v, "adam_t": int(self.t)}
+
+    def load_state_dict(self, d):
+        self.rate = float(d["rate"])
+        self.rate_decay = float(d["rate_decay"])
+        # (a checkpoint of another optimizer has no moments: start from zero, t = 0)
+        has = "adam_m" in d and "adam_v" in d
+        self.m = d["adam_m"].float().clone() if has else torch.zeros_like(self.m)
+        self.v = d["adam_v"].float().clone() if has else torch.zeros_like(self.v)
+        self.t = int(d.get("adam_t", 0)) if has else 0
+
+
+def trust_ratio(sp: float, su: float):
+    """(wn, un, phi) as fp32 values from the two sums of squares (doubles): each sum rounded to
+    fp32 (above its range: inf), its root rounded to fp32, phi = fp32(double(wn) / double(un))
+    if both norms are finite and > 0, else 1."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        wn = np.float32(np.sqrt(np.float64(np.float32(sp))))
+        un = np.float32(np.sqrt(np.float64(np.float32(su))))
+        ok = np.isfinite(wn) and np.isfinite(un) and wn > 0 and un > 0
+        phi = np.float32(np.float64(wn) / np.float64(un)) if ok else np.float32(1.0)
+    return float(wn), float(un), float(phi)
+
+
+class Lamb:
+    def __init__(self, rate: float, rate_decay: float, beta1: float, beta2: float, eps: float,
+                 weight_decay: float, numel: int, ranges=()):
+        self.rate = float(rate)
+        self.rate_decay = float(rate_decay)
+        f32 = lambda x: torch.tensor(float(x), dtype=torch.float32).item()
+        self.beta1, self.beta2, self.eps = f32(beta1), f32(beta2), f32(eps)
+        self.m = torch.zeros(numel, dtype=torch.float32)
+        self.v = torch.zeros(numel, dtype=torch.float32)
+        self.t = 0                     # applied steps: what the bias corrections count
+        # the adapted tensors ([begin, end) pairs): weight_decay inside them, 0 elsewhere
+        self.ranges = [(int(b), int(e)) for b, e in ranges]
+        self.wd = torch.zeros(numel, dtype=torch.float32)
+        for b, e in self.ranges:
+            self.wd[b:e] = float(weight_decay)
+        self._stats = [(0.0, 0.0, 1.0)] * len(self.ranges)
+
+    @torch.no_grad()
+    def step(self, params: torch.Tensor, grads: torch.Tensor):
+        self.t += 1
+        f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+        c1 = f32(1.0 / (1.0 - self.beta1 ** self.t))
+        c2 = f32(1.0 / (1.0 - self.beta2 ** self.t) ** 0.5)
+        self.m.mul_(self.beta1).add_(grads, alpha=1.0 - self.beta1)
+        self.v.mul_(self.beta2).add_((grads * (1.0 - self.beta2)).mul_(grads))
+        u = (self.m * c1).div_(self.v.sqrt().mul_(c2).add_(self.eps)).add_(self.wd * params)
+        phi = torch.ones_like(u)
+        self._stats = []
+        for b, e in self.ranges:
+            pd, ud = params[b:e].double(), u[b:e].double()
+            st = trust_ratio(float((pd * pd).sum()), float((ud * ud).sum()))
+            self._stats.append(st)
+            phi[b:e] = st[2]
+        params.sub_(u.mul_(phi.mul_(f32(self.rate))))
+        self.rate = self.rate * (1.0 - self.rate_decay)
+
+    def lamb_stats(self):
+        """Per adapted tensor (wn, un, phi) of the last applied step."""
+        return list(self._stats)
+
+    def state_dict(self):
+        # (Adam's state under Adam's keys: a checkpoint moves between adamw and lamb)
+        return {"kind": "lamb", "rate": self.rate, "rate_decay": self.rate_decay,
                 "adam_m": self.m, "adam_v": self.v, "adam_t": int(self.t)}
 
     def load_state_dict(self, d):
