@@ -16,6 +16,15 @@
 // of the useful products.  Both operands are read with transposing LDS reads
 // (ds_read_b64_tr_b16): rows = pixels (K), columns = channels.
 //
+// The three taps of a kernel row are the same eight K rows of a lane shifted by one
+// (off_t differs by 1), so only the centre tap is read from LDS (two transposing reads) and
+// the kw = 0 / 2 fragments are put together in registers: three shared v_alignbit dwords plus
+// the one row in front (m) and behind (p), one ds_read_u16 each.  Per wave and K-step: 14
+// transposing + 6 narrow reads (8 KB of LDS) instead of 26 transposing reads (13.3 KB), for
+// 24 more VALU; operands and accumulation order are bit-for-bit those of the nine-reads path,
+// which stays behind ablation bit 64.  The step's reads are ordered so that the first MFMA
+// waits for four of them, not twelve (profiles/r8_win_kw_regs.txt).
+//
 // Workgroup = 4 waves, tile 64 co x 9 taps x 64 ci (wave wn: 64 co x 9 taps x 16 ci, 4 x 9
 // accumulator fragments); grid = layers x co-chunks x ci-chunks x pixel splits, two
 // workgroups per CU, XCD-remapped so the chunks of one (layer, split) share an L2.  Output:
@@ -29,6 +38,9 @@
 using namespace dg;
 
 namespace {
+
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 constexpr int WF = 21;              // frame width (pad 1)
 constexpr int WFF = WF * WF;        // 441 rows per board
@@ -66,7 +78,9 @@ DG_DEV int step_g0(int s) {
 
 // ABL: ablation bits (diagnostics; 0 in production): 1 no MFMA, 2 no LDS reads, 4 no DMA,
 // 8 X read addresses fixed per board (no per-step address VALU; wrong data), 16 no K-step
-// barrier (races; timing only).
+// barrier (races; timing only); 32 s_setprio 1 while a step's MFMAs run (production at
+// M >= 256); 64 all nine taps read from LDS (the path before the kw shift moved into
+// registers; correct and bit-identical, kept as the A/B and the reference).
 // PD: LDS-DMA prefetch distance in K-steps (dZ buffers = PD + 1; the X ring holds the
 // current window plus PD steps ahead: <= 22 + 54 + 57 + 32 (PD - 1) + 8 rows < 256 for
 // PD <= 4).  The DMAs are issued from inline asm (dma16) with hand vmcnt accounting: every
@@ -83,6 +97,7 @@ template <int ABL, int PD, int NW>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_wgrad_win_kernel(WinArgs a, WinLayers Ls) {
   static_assert(PD >= 1 && PD <= 4, "prefetch distance");
   static_assert(NW == 4, "waves");
+  constexpr bool KWREG = !(ABL & 64);
   constexpr int COCH = 16 * NW;        // co per workgroup (64 or 128)
   constexpr int DZR = 2 * COCH;        // dZ LDS row bytes
   constexpr int DZB = 32 * DZR;        // one dZ step (32 rows); NW 1-KB blocks
@@ -188,16 +203,31 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_wgrad_win_kernel(WinArgs
 #pragma unroll
     for (int i = 0; i < 4; ++i) rel_d[h][i] = rl * DZR + (((8 * wm + 2 * i + p1) ^ sw) * 16) + p0;
   }
-  int rel_x[9][2];
+  // KWREG (the production path): per kernel row only the centre tap is read with the two
+  // transposing reads; rel_m / rel_p address the one row in front of and behind a lane's
+  // eight (2 B each, channel n = li), from which the kw = 0 / 2 fragments are shifted
+  // together in registers.  Otherwise (ABL bit 64) all nine taps are read from LDS.
+  int rel_x[9][2], rel_m[3], rel_p[3];
   auto board_rel = [&](int gb) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < 9; ++t) {
+      if (KWREG && t % 3 != 1) continue;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int off = (t / 3 - 1) * WF + (t % 3 - 1);
         const int slot = (gb + off + 8 * g + 4 * h + q) & (XR - 1);
         rel_x[t][h] = slot * 128 + (((2 * wn + p1) ^ xswz(slot)) * 16) + p0;
       }
+    }
+    if constexpr (KWREG) {
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        const int sm = (gb + (kh - 1) * WF + 8 * g - 1) & (XR - 1);
+        const int sp = (gb + (kh - 1) * WF + 8 * g + 8) & (XR - 1);
+        rel_m[kh] = sm * 128 + (((2 * wn + (li >> 3)) ^ xswz(sm)) * 16) + (li & 7) * 2;
+        rel_p[kh] = sp * 128 + (((2 * wn + (li >> 3)) ^ xswz(sp)) * 16) + (li & 7) * 2;
+      }
+    }
   };
   int bsteps = s0 / STEPS_PER_BOARD;           // board of step st
   int j = s0 - bsteps * STEPS_PER_BOARD;       // step within the board
@@ -217,6 +247,11 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_wgrad_win_kernel(WinArgs
       dma_wait<0>();
     }
   };
+  // lgkmcnt(0) in front of the loop: a kernel-argument load still pending on the path around
+  // the prologue (s0 == s1) otherwise reaches the loop head, where the compiler cannot count
+  // LDS reads behind a scalar load and makes every step's first wait a full lgkmcnt(0)
+  // instead of the counted ones below
+  if constexpr (KWREG) __builtin_amdgcn_s_waitcnt(0xC07F);
   for (int st = s0; st < s1; ++st) {
     if (st + PD < s1) issue(st + PD, buf_pd);
     if (j == STEPS_PER_BOARD) {
@@ -226,47 +261,97 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) conv_wgrad_win_kernel(WinArgs
     }
     const int jo = j * 4096;
     const char* sD = dzbuf + buf * DZB;
-    s16x4 ta[2][4], tb[2][9];
-    if constexpr (ABL & 2) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ta[h][i] = s16x4{};
-#pragma unroll
-        for (int t = 0; t < 9; ++t) tb[h][t] = s16x4{};
-      }
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ta[h][i] = lds_read_tr((const LDS_AS char*)(sD + rel_d[h][i]));
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-          tb[h][t] = lds_read_tr((const LDS_AS char*)(
-              xring + ((ABL & 8) ? rel_x[t][h] : ((rel_x[t][h] + jo) & (XRING - 1)))));
-    }
+    auto xaddr = [&](int rel) {
+      return (const LDS_AS char*)(xring + ((ABL & 8) ? rel : ((rel + jo) & (XRING - 1))));
+    };
+    // Kernel row kh of the KWREG path: c = the centre tap's eight K rows c0..c7 as dwords
+    // (c0,c1) (c2,c3) (c4,c5) (c6,c7); m = the row in front of them, p = the row behind.
+    u32x2 c[3][2] = {};
+    uint32_t m[3] = {}, p[3] = {};
+    auto c_read = [&](int kh) {
+      if constexpr (ABL & 2) return;
+      c[kh][0] = __builtin_bit_cast(u32x2, lds_read_tr(xaddr(rel_x[3 * kh + 1][0])));
+      c[kh][1] = __builtin_bit_cast(u32x2, lds_read_tr(xaddr(rel_x[3 * kh + 1][1])));
+    };
+    auto mp_read = [&](int kh) {
+      if constexpr (ABL & 2) return;
+      m[kh] = *(const LDS_AS uint16_t*)xaddr(rel_m[kh]);
+      p[kh] = *(const LDS_AS uint16_t*)xaddr(rel_p[kh]);
+    };
+    // read order of a step: centre of row 0, dZ fragments 0..3, m / p of row 0 — the first
+    // MFMA needs the first four reads only (waits lgkmcnt(8), 6, 4, 2 in front of the centre
+    // tap's four MFMAs)
+    if constexpr (KWREG) c_read(0);
     bf16x8 af[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const s16x4 lo = ta[0][i], hi = ta[1][i];
+      s16x4 lo{}, hi{};
+      if constexpr (!(ABL & 2)) {
+        lo = lds_read_tr((const LDS_AS char*)(sD + rel_d[0][i]));
+        hi = lds_read_tr((const LDS_AS char*)(sD + rel_d[1][i]));
+      }
       const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       af[i] = __builtin_bit_cast(bf16x8, v);
     }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const s16x4 lo = tb[0][t], hi = tb[1][t];
-      const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    // one tap's 4 MFMAs; the X fragment as 4 dwords of 2 K rows each (rows 8g + 2jd,
+    // 8g + 2jd + 1 of the tap's shifted window)
+    auto tap = [&](int t, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+      const u32x4 v = {x0, x1, x2, x3};
       const bf16x8 bfr = __builtin_bit_cast(bf16x8, v);
       if constexpr (ABL & 1) {
         asm volatile("" ::"v"(bfr));
       } else {
-        if constexpr (ABL & 32) __builtin_amdgcn_s_setprio(1);
+        if constexpr ((ABL & 32) && !KWREG) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i][t] = mfma16(af[i], bfr, acc[i][t]);
-        if constexpr (ABL & 32) __builtin_amdgcn_s_setprio(0);
+        if constexpr ((ABL & 32) && !KWREG) __builtin_amdgcn_s_setprio(0);
       }
+    };
+    if constexpr (KWREG) {
+      // The kw = 0 / 2 fragments are the centre's rows shifted by one: (m,c0) s0 s1 s2 and
+      // s0 s1 s2 (c7,p) with s_j = (c_{2j+1}, c_{2j+2}), one v_alignbit / v_perm each.  Per
+      // row: the centre tap, then the reads of row kh + 1, then the two shifted taps.  The
+      // scheduling barriers pin that order: left alone, the scheduler sinks each row's reads
+      // to just before their use and hoists the shifts in front of the first wait.
+      // ABL bit 32 raises the priority ONCE per step, over the shifts and reads as well: with
+      // s_setprio around each tap only, the VALU and reads between the taps wait at priority 0
+      // behind the other workgroup's MFMAs (10 x 256: 1049 us, against 925 us like this and
+      // 1006 us on the nine-taps path; profiles/r8_win_kw_regs.txt).
+      mp_read(0);
+      if constexpr (ABL & 32) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+      }
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        __builtin_amdgcn_sched_barrier(0);
+        const uint32_t d0 = c[kh][0][0], d1 = c[kh][0][1], d2 = c[kh][1][0], d3 = c[kh][1][1];
+        tap(3 * kh + 1, d0, d1, d2, d3);
+        __builtin_amdgcn_sched_barrier(0);
+        if (kh < 2) {
+          c_read(kh + 1);
+          mp_read(kh + 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        const uint32_t s0 = __builtin_amdgcn_alignbit(d1, d0, 16);
+        const uint32_t s1 = __builtin_amdgcn_alignbit(d2, d1, 16);
+        const uint32_t s2 = __builtin_amdgcn_alignbit(d3, d2, 16);
+        tap(3 * kh, (d0 << 16) | m[kh], s0, s1, s2);
+        tap(3 * kh + 2, s0, s1, s2, __builtin_amdgcn_alignbit(p[kh], d3, 16));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (ABL & 32) __builtin_amdgcn_s_setprio(0);
+    } else {
+      u32x2 x[9][2] = {};
+      if constexpr (!(ABL & 2)) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            x[t][h] = __builtin_bit_cast(u32x2, lds_read_tr(xaddr(rel_x[t][h])));
+      }
+#pragma unroll
+      for (int t = 0; t < 9; ++t) tap(t, x[t][0][0], x[t][0][1], x[t][1][0], x[t][1][1]);
     }
     wait_next(st);
     if constexpr (!(ABL & 16)) __syncthreads();
@@ -335,17 +420,29 @@ hipError_t dg_conv_wgrad_win(const long long* table, int nl, int M, int Mpad, in
   }
   WinArgs a{sf, M, Mpad, Cx, KP, B, splits, nl};
   const dim3 grid(nl * (M / coch) * (Cx / 64) * splits);
-  // d >= 256: s_setprio 1 around each tap's MFMAs (ABL bit 32).  This kernel is the step's
+  // d >= 256: s_setprio 1 over each step's MFMAs (ABL bit 32; around each tap's on the
+  // nine-taps path).  This kernel is the step's
   // critical path there and the side stream's bias partials / 5x5 weight gradient share its
   // CUs: 12x256 bf16 +1.6%; at d = 128 the side chain is the critical one (-2.9%), and the
   // same priority on the MX-fp8 window kernel, the side kernels or the stacks measured equal
   // or slower (profiles/r4_s2_wave_priority_ab.txt)
+  // bit 64: the nine-taps-from-LDS read path (correct results, bit-identical slabs: the
+  // in-tree A/B and reference of the kw-from-registers path); combines with 0 and 32 only
+  const bool lds9 = (g_win_ablate & 64) != 0;
   if (M >= 256 && (g_win_ablate & 31) == 0) {
-    launch_win<32>(grid, a, Ls, stream);
+    if (lds9)
+      launch_win<32 | 64>(grid, a, Ls, stream);
+    else
+      launch_win<32>(grid, a, Ls, stream);
     return hipGetLastError();
   }
   switch (g_win_ablate & 31) {
-    case 0: launch_win<0>(grid, a, Ls, stream); break;
+    case 0:
+      if (lds9)
+        launch_win<64>(grid, a, Ls, stream);
+      else
+        launch_win<0>(grid, a, Ls, stream);
+      break;
 #define WIN_CASE(n) \
   case n:           \
     launch_win<n>(grid, a, Ls, stream); \
