@@ -1114,10 +1114,33 @@ static int reduce_grid_x(const ReduceLayers& Ls, int i) {
   return Ls.main_blocks[i] + (Ls.bpart[i] ? (NPTS * Ls.M[i] + 255) / 256 + Ls.M[i] : 0);
 }
 
+// What wgrad_reduce_kernel relies on, for one layer (dg_api.h dg_wgrad_reduce): 16-byte slab
+// loads of 4 consecutive k, a non-zero cinp to divide by, every out entry inside taps * cinp
+// columns of the slab, and M * (KP / 4) work items that fit the kernel's int index.
+static bool reduce_layer_ok(const float* slab, const float* out, const float* bpart,
+                            const float* gposb, const float* gbias, long long splits,
+                            long long M, long long Mpad, long long KP, long long taps,
+                            long long cin, long long cinp, long long bchunks) {
+  constexpr long long IMAX = 0x7fffffffLL;
+  if (!slab || !out || ((uintptr_t)slab & 15) != 0) return false;
+  if (splits < 1 || splits > IMAX || M < 1 || M > Mpad || Mpad > IMAX) return false;
+  if (KP <= 0 || KP > IMAX || KP % 4 != 0) return false;
+  if (taps < 1 || taps > IMAX || cin < 1 || cin > cinp || cinp > IMAX) return false;
+  if (taps * cinp > KP) return false;
+  // (the grid-stride loop steps its int index by up to 8192 x 256 past the last item)
+  if (M * (KP / 4) > IMAX - 8192 * 256) return false;
+  if (bpart && (bchunks < 1 || bchunks > IMAX || !gposb || !gbias || M > IMAX / NPTS))
+    return false;
+  return true;
+}
+
 hipError_t dg_wgrad_reduce(const float* slab, float* out, int splits, int M, int Mpad, int KP,
                            int taps, int cin, int cinp, const float* bpart, int bchunks,
                            float* gposb, float* gbias, void* out16, void* gposb16, void* gbias16,
                            long long* sf, hipStream_t stream) {
+  if (!reduce_layer_ok(slab, out, bpart, gposb, gbias, splits, M, Mpad, KP, taps, cin, cinp,
+                       bchunks))
+    return hipErrorInvalidValue;
   ReduceLayers Ls{};
   Ls.sf = sf;
   reduce_layer(Ls, 0, slab, out, bpart, gposb, gbias, splits, M, Mpad, KP, taps, cin, cinp,
@@ -1131,7 +1154,8 @@ hipError_t dg_wgrad_reduce(const float* slab, float* out, int splits, int M, int
 }
 
 hipError_t dg_wgrad_reduce_multi(const long long* table, int nl, int cols, hipStream_t stream) {
-  if (nl <= 0 || nl > RD_MAXL || (cols != 13 && cols != 16)) return hipErrorInvalidValue;
+  if (!table || nl <= 0 || nl > RD_MAXL || (cols != 13 && cols != 16))
+    return hipErrorInvalidValue;
   ReduceLayers Ls{};
   int gx = 1;
   for (int i = 0; i < nl; ++i) {
@@ -1141,7 +1165,10 @@ hipError_t dg_wgrad_reduce_multi(const long long* table, int nl, int cols, hipSt
       Ls.gposb16[i] = (bf16_t*)t[14];
       Ls.gbias16[i] = (bf16_t*)t[15];
     }
-    if (!t[0] || !t[1] || !t[2] || t[5] <= 0 || t[6] <= 0 || t[8] % 4 != 0)
+    // (the table's integers are int64: checked at that width, narrowed after)
+    if (!t[2] || !reduce_layer_ok((const float*)t[0], (const float*)t[1], (const float*)t[2],
+                                  (const float*)t[3], (const float*)t[4], t[5], t[6], t[7], t[8],
+                                  t[9], t[10], t[11], t[12]))
       return hipErrorInvalidValue;
     reduce_layer(Ls, i, (const float*)t[0], (float*)t[1], (const float*)t[2], (float*)t[3],
                  (float*)t[4], (int)t[5], (int)t[6], (int)t[7], (int)t[8], (int)t[9],

@@ -48,15 +48,21 @@ hipError_t dg_conv_wgrad(int kw, const void* dZ, int dz_pad, int M, int Mpad, co
 hipError_t dg_conv_wgrad_multi(int kw, const long long* table, int nl, int dz_pad, int M,
                                int Mpad, int x_pad, int x_C, int B, int KP, int splits,
                                hipStream_t stream);
-// Slab reduce + bias-gradient pass 2 of one layer; out16 / gposb16 / gbias16 (optional): bf16
-// twins of the weight / position-bias / bias gradients.
+// Slab reduce + bias-gradient pass 2 of one layer; out16 / gposb16 / gbias16 (optional, each
+// on its own): bf16 twins of the weight / position-bias / bias gradients.  Refused unless:
+// slab (16-byte aligned) and out are given; splits >= 1; 1 <= M <= Mpad; KP > 0 and a multiple
+// of 4; taps >= 1; 1 <= cin <= cinp; taps * cinp <= KP (else part of out would never be
+// written); M * (KP / 4) fits an int with room for the grid stride; and, when bpart
+// (optional) is given, bchunks >= 1 and both gposb and gbias.
 hipError_t dg_wgrad_reduce(const float* slab, float* out, int splits, int M, int Mpad, int KP,
                            int taps, int cin, int cinp, const float* bpart, int bchunks,
                            float* gposb, float* gbias, void* out16, void* gposb16,
                            void* gbias16, long long* sf, hipStream_t stream);
 // Slab reduce + bias-gradient pass 2 of nl layers (any shapes) in one launch: table = nl
 // rows of `cols` int64 {slab, out (weight grad), bpart, gposb, gbias, splits, M, Mpad, KP,
-// taps, cin, cinp, bchunks[, out16, gposb16, gbias16]} (cols 13, or 16 with bf16 twins).
+// taps, cin, cinp, bchunks[, out16, gposb16, gbias16]} (cols 13, or 16 with bf16 twins, each
+// optional on its own).  1 <= nl <= 16; every row must satisfy dg_wgrad_reduce's rules (the
+// int64 columns are checked before they are narrowed) and bpart is required.
 hipError_t dg_wgrad_reduce_multi(const long long* table, int nl, int cols, hipStream_t stream);
 
 // ---------------------------------------------------------------- conv_board.hip

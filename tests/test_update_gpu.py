@@ -629,7 +629,8 @@ def test_train_step_matches_references(name, fused, monkeypatch):
     bf16 wire twin is the fp32 gradient rounded once; every operand copy the step refreshes
     equals the layouts of the NEW parameters.  (On the deferred path the reported gradient is
     written by the update launch itself: that its slab and partial sums are right rests on
-    test_fused_update_matches_separate_launches and the gradient oracles, not on this test.)
+    tests/test_grad_reduce_gpu.py — test_grad_update_deferred_exact_on_integer_data and
+    test_grad_update_deferred_matches_reduce_and_documented_order — not on this test.)
 
     Measured on an MI355X (RMSProp configs, both paths alike): ms within 1.2 x 2^-24, the
     update within 1.4 x 2^-24 |d| where p's final rounding is negligible."""
