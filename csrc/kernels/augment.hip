@@ -4,8 +4,8 @@
 // oracle of the whole transform).  The launcher is built into its own small extension, _dgaug
 // (aug_bindings.cpp).
 //
-// A point is p = 19 x + y.  For s in 0..7, T_s maps (x, y): if s & 4 first swap to (y, x), then
-// apply (a, b) -> (b, 18 - a) exactly s & 3 times.  s = 0 is the identity.
+// The symmetries T_s, s in 0..7, of a point p = 19 x + y are sym_fwd / sym_inv of dg_common.h,
+// the ones the predictor's ensemble (policy.hip) uses.
 //
 // The symmetry of a board is a pure 32-bit integer hash of (seed, loader sequence number, board
 // index): no generator state, so a resumed run draws what the uninterrupted one would have, and
@@ -37,22 +37,6 @@ __host__ __device__ inline int hash_symmetry(unsigned long long seed, unsigned l
   const uint32_t a = mix32(((uint32_t)seed ^ 0x9e3779b9u) + (uint32_t)(seed >> 32));
   const uint32_t b = mix32(mix32(a + (uint32_t)seq) ^ (uint32_t)(seq >> 32));
   return (int)(mix32(b + (uint32_t)board) >> 29);
-}
-
-// T_s(p)
-DG_DEV int sym_fwd(int s, int p) {
-  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
-  if (s & 4) { const int t = a; a = b; b = t; }
-  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = b; b = BOARD - 1 - t; }
-  return a * BOARD + b;
-}
-
-// T_s^-1(p): undo the rotations ((a, b) -> (18 - b, a)), then the swap
-DG_DEV int sym_inv(int s, int p) {
-  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
-  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = BOARD - 1 - b; b = t; }
-  if (s & 4) { const int t = a; a = b; b = t; }
-  return a * BOARD + b;
 }
 
 // One workgroup per board i: s = sym[i] & 7 when sym is given, else the hash of (seed, seq,

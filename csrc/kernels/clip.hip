@@ -48,18 +48,6 @@ struct ClipRecord {
 };
 static_assert(sizeof(ClipRecord) == 16, "the record's layout is part of the interface");
 
-// as optim.hip: gradient 4-vector i4 from the flat fp32 gradient (16-byte load) or from its
-// bf16 wire twin (8-byte load), widened exactly
-DG_DEV float grad_at(const float* g, size_t i) { return g[i]; }
-DG_DEV float grad_at(const bf16_t* g, size_t i) { return bf2f(g[i]); }
-DG_DEV f32x4 grad4_raw(const float* g, size_t i4) { return ((const f32x4*)g)[i4]; }
-DG_DEV uint2 grad4_raw(const bf16_t* g, size_t i4) { return ((const uint2*)g)[i4]; }
-DG_DEV f32x4 grad4_f32(const f32x4 raw) { return raw; }
-DG_DEV f32x4 grad4_f32(const uint2 u) {
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-               __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
-}
-
 // Workgroup blockIdx.x's share of sum g[i]^2.  Thread tid takes 4-vector c0 + tid of every pass
 // c0 = (blockIdx.x + k gridDim.x) MT and adds its four squares to one fp32 chain, element by
 // element, passes in increasing k (the loads of AHEAD passes are issued together; the order of
@@ -104,12 +92,6 @@ gradnorm_partial(const G* __restrict__ g, size_t n, float* __restrict__ part,
   if ((tid & 63) == 0) s_w[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) part[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
-DG_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Every workgroup: S = the sum of the np <= CLIP_PARTIALS partials in double, thread t taking

@@ -24,9 +24,6 @@ using namespace dg;
 
 namespace {
 
-constexpr int EPI_LINEAR = 0;
-constexpr int EPI_FWD = 1;
-constexpr int EPI_DGRAD = 2;
 constexpr int NCOL = 384;
 
 struct BoardArgs {

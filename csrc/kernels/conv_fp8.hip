@@ -23,20 +23,10 @@
 
 using namespace dg;
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
 namespace {
 
 constexpr int NCOL = 384;
 constexpr float FP8_MAX = 448.f;
-
-DG_DEV uint32_t pack_fp8x4(float a, float b, float c, float d) {
-  // v_cvt_pk_fp8_f32: two floats -> two e4m3 bytes in the low / high word half
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
 
 struct Fp8Args {
   const uint8_t* A;    // [Mpad][KP] e4m3 weights, k = tap*x_C + ci

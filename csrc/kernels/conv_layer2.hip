@@ -17,7 +17,7 @@
 // Reference ops: SpatialConvolutionMM + Add + ReLU (experiments.lua:137-147) and their
 // backward (train.lua:10).
 #include "dg_api.h"
-#include "dg_common.h"
+#include "dg_frame.h"
 #include "head_body.h"
 
 #include <cstdlib>
@@ -26,13 +26,7 @@ using namespace dg;
 
 namespace {
 
-constexpr int EPI_FWD = 1;
-constexpr int EPI_DGRAD = 2;
-constexpr int F = 21;
-constexpr int FF = F * F;
-constexpr int HROWS = 448;
 constexpr int H_BYTES = HROWS * 128;       // one 64-channel chunk image
-constexpr int T = 9;
 constexpr int MF = 4, NF = 6;              // wave tile 64 co x 96 px
 constexpr int NW = 8, NT = NW * 64;
 constexpr int STEP_BYTES = 2 * 2 * MF * 64 * 16;   // 16 KB: one K-step of one co half
@@ -48,32 +42,6 @@ struct LayerArgs {
   uint8_t* mask;         // [B][361][C/8]: EPI_FWD writes, EPI_DGRAD reads (layer below)
   int C;
 };
-
-DG_DEV int fsig(int f) { return ((f % F) + 3 * (f / F)) & 7; }
-
-DG_DEV void lds_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_s_barrier();
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-DG_DEV uint32_t bf16x2_bits(f32x2 v) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v));
-}
-DG_DEV uint32_t relu_bf16x2(f32x2 v) {
-  const s16x2 h = __builtin_bit_cast(s16x2, __builtin_convertvector(v, bf16x2v));
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(h, s16x2{0, 0}));
-}
-DG_DEV f32x2 bf16x2_f32(uint32_t u) {
-  return f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xFFFF0000u)};
-}
-DG_DEV uint32_t pair_mask(uint32_t nib) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 0, 1);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 1, 1);
-  return __builtin_amdgcn_perm(hi, lo, 0x07060100u);
-}
 
 template <int EPI>
 __global__ void __launch_bounds__(NT) conv_layer2_kernel(LayerArgs a) {

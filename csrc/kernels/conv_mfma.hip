@@ -29,10 +29,6 @@ using namespace dg;
 
 namespace {
 
-constexpr int EPI_LINEAR = 0;
-constexpr int EPI_FWD = 1;
-constexpr int EPI_DGRAD = 2;
-
 struct ConvNTArgs {
   const bf16_t* A;     // [Mpad][KP] bf16 weights (K contiguous)
   const char* X;       // input frame (bytes)

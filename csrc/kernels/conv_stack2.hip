@@ -41,22 +41,16 @@
 #include <stdlib.h>
 
 #include "dg_api.h"
-#include "dg_common.h"
 #include "dg_features.h"
+#include "dg_frame.h"
 #include "head_body.h"
 
 using namespace dg;
 
 namespace {
 
-constexpr int EPI_FWD = 1;
-constexpr int EPI_DGRAD = 2;
 constexpr int C = 128;
-constexpr int F = 21;                     // 19 + 2 * pad(1)
-constexpr int FF = F * F;                 // 441
-constexpr int HROWS = 448;                // halo rows padded to whole 8-wave DMA rounds
 constexpr int H_BYTES = HROWS * 128;      // one 64-channel image
-constexpr int T = 9;
 constexpr int NSTEP = 2 * T;              // chunks x taps
 constexpr int MAXL = 24;
 constexpr int MF = 4;                     // 64 co per wave (4 fragments of 16)
@@ -99,8 +93,6 @@ struct StackArgs {
   int stag_delay;
 };
 
-DG_DEV int fsig(int f) { return ((f % F) + 3 * (f / F)) & 7; }
-
 // The network's first layer fused in front of the forward stack (l1 mode): 5x5 over the
 // zero-bordered 23x23 frame of the 37 input planes padded to 40 channels (80 B per pixel),
 // staged linearly into the (still unused) image area.  K runs over the 125 8-channel
@@ -126,35 +118,7 @@ constexpr int L1_CELLS = 5 * L1PS;               // 4080 (65,280 B)
 constexpr int L1_STEPS = 16;
 constexpr int L1_CHUNKS = 125;
 
-// s_waitcnt lgkmcnt(0) (LDS writes of this wave done), vmcnt/expcnt untouched, then barrier:
-// unlike __syncthreads() this does not drain the weight loads already in flight
-DG_DEV void lds_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_s_barrier();
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 (RNE, v_cvt_pk_bf16_f32)
-DG_DEV uint32_t bf16x2_bits(f32x2 v) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v));
-}
-// ... then ReLU as a packed int16 max with 0 (v_pk_max_i16)
-DG_DEV uint32_t relu_bf16x2(f32x2 v) {
-  const s16x2 h = __builtin_bit_cast(s16x2, __builtin_convertvector(v, bf16x2v));
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(h, s16x2{0, 0}));
-}
-// packed bf16 pair -> two fp32
-DG_DEV f32x2 bf16x2_f32(uint32_t u) {
-  return f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xFFFF0000u)};
-}
-// bits 0 / 1 of nib -> 0xffff / 0xffff0000 halves (v_bfe_i32 x 2 + v_perm_b32)
-DG_DEV uint32_t pair_mask(uint32_t nib) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 0, 1);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)nib, 1, 1);
-  return __builtin_amdgcn_perm(hi, lo, 0x07060100u);
-}
+// (lds_barrier and the packed-bf16 epilogue helpers: dg_frame.h)
 
 // packed 16-bit halves in [0, 0x7fff] (post-ReLU bf16) -> 1 where the half is nonzero: one
 // v_pk_min_i16 with 1 (signed on purpose: the compiler rewrites the unsigned min as compares

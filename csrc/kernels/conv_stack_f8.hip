@@ -49,21 +49,14 @@
 #include <stdlib.h>
 
 #include "dg_api.h"
-#include "dg_common.h"
+#include "dg_frame.h"
 #include "head_body.h"
 
 using namespace dg;
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
 namespace {
 
-constexpr int F = 21;
-constexpr int FF = F * F;                 // 441
-constexpr int HROWS = 448;
 constexpr int H_BYTES = HROWS * 128;      // one bf16 64-channel image (C = 128 last layer)
-constexpr int T = 9;                      // taps
 constexpr int MAXL = 24;
 constexpr int MF = 4;                     // 64 co per wave
 constexpr int NF = 6;                     // 96 px per wave
@@ -74,8 +67,6 @@ constexpr int STEP_BYTES = 2 * MF * 2 * 64 * 16;  // 16 KB per (tap, chunk) K-st
 constexpr int WM_BYTES = STEP_BYTES / 2;
 constexpr float FP8_MAX = 448.f;      // e4m3
 constexpr float BF8_MAX = 57344.f;    // e5m2
-constexpr int EPI_FWD = 1;
-constexpr int EPI_DGRAD = 2;
 constexpr int FP8P = 448;             // fp8 copy-out frames: rows per board
 constexpr int IMG2 = 61440;           // C = 128 staggered schedule: second image's offset
 
@@ -131,8 +122,9 @@ struct F8Args {
   dghead::HeadMArgs head;
 };
 
-// swizzle signature of frame row f (16-B slot s of the row lives at s ^ sig): a table over
-// v = (x + 3y) & 7, which steps by 1 along raster order (also across a board-row wrap, and by
+// swizzle signature of frame row f of the fp8 image (16-B slot s of the row lives at s ^ sig): a
+// table over v = fsig(f) = (x + 3y) & 7 (dg_frame.h: the bf16 image's signature), which steps
+// by 1 along raster order (also across a board-row wrap, and by
 // tsig = dx + 3 dy for a tap).  A B-fragment read (ds_read_b128) serves lanes in 4 groups of
 // 16 that mix two lane groups lq (slots 8c + 2lq + h): the sig must not disturb bit 1 of the
 // slot there.  C = 256: v's bits spread to slot bits {0, 2, 3}; C = 128 (8 slots, two rows
@@ -144,21 +136,8 @@ DG_DEV int sig_of(int v) {
   constexpr uint32_t TAB = C == 128 ? 0x60147107u : 0xDC985410u;
   return (int)((TAB >> (4 * (v & 7))) & 15u);
 }
-DG_DEV int fv(int f) { return ((f % F) + 3 * (f / F)) & 7; }
 template <int C>
-DG_DEV int fsig(int f) { return sig_of<C>(fv(f)); }
-DG_DEV int fsig8(int f) { return ((f % F) + 3 * (f / F)) & 7; }
-
-DG_DEV void lds_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0), vmcnt / expcnt untouched
-  __builtin_amdgcn_s_barrier();
-}
-
-DG_DEV uint32_t pack_fp8x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
+DG_DEV int fsig_f8(int f) { return sig_of<C>(fsig(f)); }
 
 // workgroup max of non-negative v folded into *amax (one atomic per workgroup); s_tmp: 8
 // floats of LDS; every thread calls it (contains a barrier)
@@ -309,7 +288,7 @@ __global__ void __launch_bounds__(NT) conv_stack_f8_kernel(F8Args a) {
       const uint32_t key = sr_seed + (uint32_t)((b * FF + f) * C + q * 8);
       o.x = pack8x4q<EPI, MODE>(x[0], x[1], x[2], x[3], key);
       o.y = pack8x4q<EPI, MODE>(x[4], x[5], x[6], x[7], key + 4);
-      *(uint2*)(sI + f * ROWB + (((q >> 1) ^ fsig<C>(f)) * 16) + (q & 1) * 8) = o;
+      *(uint2*)(sI + f * ROWB + (((q >> 1) ^ fsig_f8<C>(f)) * 16) + (q & 1) * 8) = o;
       // the fp8 copy of the quantized input (the fp8 weight gradient's operand)
       if constexpr ((MODE & 8) != 0) *(uint2*)(a.X8_0 + ((size_t)(b * FP8P + f) * C + q * 8)) = o;
     }
@@ -348,7 +327,7 @@ __global__ void __launch_bounds__(NT) conv_stack_f8_kernel(F8Args a) {
         const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
         f = (h + 1) * F + (w + 1);
       }
-      pk[j] = (uint32_t)(f * ROWB) | ((uint32_t)fv(f) << 20);
+      pk[j] = (uint32_t)(f * ROWB) | ((uint32_t)fsig(f) << 20);
     }
   };
   const uint32_t a_lane = (uint32_t)(wm * WM_BYTES + lane * 16);
@@ -427,7 +406,7 @@ __global__ void __launch_bounds__(NT) conv_stack_f8_kernel(F8Args a) {
     co_pq(s_, tid, p, q);
     const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
     const int f = (h + 1) * F + (w + 1);
-    return *(const uint4*)(sI + img_rd + f * ROWB + ((q ^ fsig<C>(f)) * 16));
+    return *(const uint4*)(sI + img_rd + f * ROWB + ((q ^ fsig_f8<C>(f)) * 16));
   };
   // (y8: the fp8 copy of the previous layer's output, or null)
   // (yb / y8b: the bf16 / fp8 output frames advanced to this board, per layer)
@@ -503,7 +482,7 @@ __global__ void __launch_bounds__(NT) conv_stack_f8_kernel(F8Args a) {
       const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
       const int f = (h + 1) * F + (w + 1);
       const uint4 v =
-          *(const uint4*)(sI + (co_q >> 3) * H_BYTES + f * 128 + (((co_q & 7) ^ fsig8(f)) * 16));
+          *(const uint4*)(sI + (co_q >> 3) * H_BYTES + f * 128 + (((co_q & 7) ^ fsig(f)) * 16));
       *(uint4*)(Ll.Y + ((size_t)(b * FF + f) * C) * 2 + co_q * 16) = v;
       typedef unsigned short us2 __attribute__((ext_vector_type(2)));
       auto nz2 = [](uint32_t x) {

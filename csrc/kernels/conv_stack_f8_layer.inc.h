@@ -289,7 +289,7 @@
           uint2 o;
           o.x = pack_bf16x2(v[0], v[1]);
           o.y = pack_bf16x2(v[2], v[3]);
-          *(uint2*)(sIe + wm * H_BYTES + f * 128 + (((cw >> 3) ^ fsig8(f)) * 16) + (cw & 4) * 2) = o;
+          *(uint2*)(sIe + wm * H_BYTES + f * 128 + (((cw >> 3) ^ fsig(f)) * 16) + (cw & 4) * 2) = o;
         } else {
           // last layer (C = 256 forward, any dgrad): bf16 straight to the output frame
           // (+ the forward's ReLU bits)
@@ -320,7 +320,7 @@
         const uint4 v = *(const uint4*)(pr + z0 + ((q ^ (p & 7)) * 16));
         const int h = p / BOARD, w = p - (p / BOARD) * BOARD;
         const int f = (h + 1) * F + (w + 1);
-        *(uint4*)(sIe + f * ROWB + ((q ^ fsig<C>(f)) * 16)) = v;
+        *(uint4*)(sIe + f * ROWB + ((q ^ fsig_f8<C>(f)) * 16)) = v;
       }
     }
   }

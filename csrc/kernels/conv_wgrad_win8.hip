@@ -53,9 +53,6 @@
 
 using namespace dg;
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
 namespace {
 
 constexpr int WF = 21;

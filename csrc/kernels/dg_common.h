@@ -13,12 +13,42 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((ext_vector_type(8))) int i32x8;   // the fp8 MFMAs' operands
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
 typedef uint16_t bf16_t;  // storage type for bf16 in global memory
 
 namespace dg {
 
 constexpr int BOARD = 19;
 constexpr int NPTS = 361;
+
+// what a conv kernel's epilogue does with its accumulators (_dghip exports the same numbers)
+constexpr int EPI_LINEAR = 0;   // stores them
+constexpr int EPI_FWD = 1;      // forward: + bias table, ReLU
+constexpr int EPI_DGRAD = 2;    // backward-data: * ReLU mask of the layer below
+
+// The eight board symmetries.  A point is p = 19 x + y.  For s in 0..7, T_s maps (x, y): if
+// s & 4 first swap to (y, x), then apply (a, b) -> (b, 18 - a) exactly s & 3 times; s = 0 is the
+// identity (deep_go_amd/data/symmetry.py is the definition).  The predictor's ensemble
+// (policy.hip) and the training-time augmentation (augment.hip) must agree on them.
+// T_s(p)
+DG_DEV int sym_fwd(int s, int p) {
+  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
+  if (s & 4) { const int t = a; a = b; b = t; }
+  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = b; b = BOARD - 1 - t; }
+  return a * BOARD + b;
+}
+// T_s^-1(p): undo the rotations ((a, b) -> (18 - b, a)), then the swap
+DG_DEV int sym_inv(int s, int p) {
+  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
+  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = BOARD - 1 - b; b = t; }
+  if (s & 4) { const int t = a; a = b; b = t; }
+  return a * BOARD + b;
+}
 
 // f32 -> bf16 round-to-nearest-even (NaN kept NaN via the compiler's v_cvt_pk_bf16_f32).
 DG_DEV bf16_t f2bf(float f) {
@@ -29,6 +59,13 @@ DG_DEV float bf2f(bf16_t u) { return __uint_as_float(((uint32_t)u) << 16); }
 
 DG_DEV uint32_t pack_bf16x2(float lo, float hi) {
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+}
+
+// four fp32 -> four e4m3 bytes (v_cvt_pk_fp8_f32: two floats into the low / high word half)
+DG_DEV uint32_t pack_fp8x4(float a, float b, float c, float d) {
+  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+  return (uint32_t)v;
 }
 
 // Async 16-byte global->LDS copy.  The LDS destination is (wave-uniform base) + lane*16.
@@ -139,6 +176,12 @@ DG_DEV float wave_sum(float v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// the same butterfly in double: every lane ends with the same bits
+DG_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 DG_DEV float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -162,6 +205,24 @@ DG_DEV void block_amax(float v, unsigned* amax, float* s_tmp) {
       atomicMax(amax, u);
   }
 }
+
+// ---- the flat gradient vector, as the update kernels read it -------------------------------
+// Element i as fp32 from the flat fp32 gradient, or from its bf16 twin (the data-parallel wire
+// format: the all-reduced bucket is read as it came off the wire); 4-vector i4 likewise, a
+// 16-byte or an 8-byte load.  grad4_raw loads the bits and grad4_f32 widens them (exactly), so a
+// kernel can issue the load early and wait for it only where the update needs the values;
+// grad4_at does both at once.
+DG_DEV float grad_at(const float* g, size_t i) { return g[i]; }
+DG_DEV float grad_at(const bf16_t* g, size_t i) { return bf2f(g[i]); }
+DG_DEV f32x4 grad4_raw(const float* g, size_t i4) { return ((const f32x4*)g)[i4]; }
+DG_DEV uint2 grad4_raw(const bf16_t* g, size_t i4) { return ((const uint2*)g)[i4]; }
+DG_DEV f32x4 grad4_f32(const f32x4 raw) { return raw; }
+DG_DEV f32x4 grad4_f32(const uint2 u) {
+  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
+               __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
+}
+template <typename G>
+DG_DEV f32x4 grad4_at(const G* g, size_t i4) { return grad4_f32(grad4_raw(g, i4)); }
 
 // ---- deterministic second-pass sums of the weight / bias gradient partials -------------
 // Shared by the slab reduce (conv_mfma.hip wgrad_reduce_kernel) and the fused reduce +

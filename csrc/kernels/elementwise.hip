@@ -174,16 +174,8 @@ bias_grad_partial_kernel(BiasLayers Ls, int B, int C, int pad, int nchunks, int 
 }
 
 // ------------------------------------------------------------------------------------
-// gradient element i as fp32: the flat fp32 gradient, or its bf16 twin (the data-parallel
-// bf16 wire format: the all-reduced bucket is read as it came off the wire)
-DG_DEV float grad_at(const float* g, size_t i) { return g[i]; }
-DG_DEV float grad_at(const bf16_t* g, size_t i) { return bf2f(g[i]); }
-DG_DEV f32x4 grad4_at(const float* g, size_t i4) { return ((const f32x4*)g)[i4]; }
-DG_DEV f32x4 grad4_at(const bf16_t* g, size_t i4) {
-  const uint2 u = ((const uint2*)g)[i4];
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-               __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
-}
+// (the gradient as fp32, from the flat fp32 gradient or its bf16 wire twin: grad_at / grad4_at,
+// dg_common.h)
 
 // SGD (optimizer.lua:24-27): theta -= lr * g over the flat fp32 master buffer.  lr lives
 // on the device (double) so the step can be replayed inside a hipGraph.

@@ -20,8 +20,6 @@
 
 using namespace dg;
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
-
 namespace {
 
 constexpr int HT = 512;      // threads per board (8 waves: 2 per SIMD)

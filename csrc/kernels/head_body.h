@@ -5,17 +5,13 @@
 #pragma once
 #include <math.h>
 
-#include "dg_common.h"
+#include "dg_frame.h"
 
 namespace dghead {
 
 using namespace dg;
 
-constexpr int F = 21;
-constexpr int FF = F * F;          // 441
-constexpr int HROWS = 448;
 constexpr int HB = HROWS * 128;    // one 64-channel image
-constexpr int T = 9;
 constexpr int DZM = 32;            // margin of the frame-shaped dz array (taps reach +-22)
 constexpr int DZN = DZM + HROWS + DZM;
 constexpr int HT = 512;
@@ -35,9 +31,6 @@ struct HeadMArgs {
   int head_relu;
   float grad_scale;
 };
-
-DG_DEV int fsig(int f) { return ((f % F) + 3 * (f / F)) & 7; }
-DG_DEV int toff_of(int t) { return (t / 3 - 1) * F + (t % 3 - 1); }
 
 // x -> (hi, lo) bf16 pair, x ~= hi + lo
 DG_DEV void split_bf(float x, uint16_t& hi, uint16_t& lo) {

@@ -1,33 +1,8 @@
 // pybind11 bindings of optim.hip's LAMB (module `_dglamb`): Adam's update rescaled per
-// conv-weight tensor by a trust ratio.  Its own extension, imported only for optimizer=lamb:
-// `_dghip`'s recorded interface and the pinned names of `_dgopt` and `_dgadam` stay as they
-// are.  Built from the same optim.hip, so the range table, the chunk lookup, the gradient loads
-// and the count's launch exist once.  Conventions as in adam_bindings.cpp: tensors cross as raw
-// device addresses, the range table as the address of a host int64 array, the stream as its
-// handle; a launcher's error becomes RuntimeError("<name>: <hipGetErrorString>").  dg_api.h
-// declares dg_lamb and dg_lamb_partials.
-#include <pybind11/pybind11.h>
-
-#include <stdexcept>
-#include <string>
-
-#include "dg_api.h"
-
-namespace py = pybind11;
-
-namespace {
-
-template <typename T>
-T* P(uintptr_t v) {
-  return reinterpret_cast<T*>(v);
-}
-
-void check(hipError_t e, const char* what) {
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-}  // namespace
+// conv-weight tensor by a trust ratio.  Its own extension, imported only for optimizer=lamb.
+// dg_api.h declares dg_lamb and dg_lamb_partials; dg_bind.h says how they cross the boundary
+// (the range table is the address of a host int64 array).
+#include "dg_bind.h"
 
 PYBIND11_MODULE(_dglamb, m) {
   m.doc() = "deep_go_amd LAMB: layer-wise trust ratios on Adam (gfx950)";
@@ -38,7 +13,7 @@ PYBIND11_MODULE(_dglamb, m) {
     check(dg_lamb(P<float>(p), P<float>(g), P<float>(mom), P<float>(v), P<float>(u), n,
                   P<double>(lr), P<void>(rec), P<float>(part), part_n, P<float>(tab), beta1,
                   beta2, eps, wd, P<long long>(ranges), n_ranges, gscale, P<float>(gate),
-                  nullptr, reinterpret_cast<hipStream_t>(stream)),
+                  nullptr, S(stream)),
           "lamb");
   }, "tick rec {t, c1, c2}; m, v moments; u = c1 m / (sqrt(v) c2 + eps) [+ wd p in ranges]; "
      "tab[k] = {|p_k|, |u_k|, phi_k}; p -= lr phi u");
@@ -50,7 +25,7 @@ PYBIND11_MODULE(_dglamb, m) {
     check(dg_lamb(P<float>(p), nullptr, P<float>(mom), P<float>(v), P<float>(u), n,
                   P<double>(lr), P<void>(rec), P<float>(part), part_n, P<float>(tab), beta1,
                   beta2, eps, wd, P<long long>(ranges), n_ranges, gscale, P<float>(gate),
-                  P<void>(g16), reinterpret_cast<hipStream_t>(stream)),
+                  P<void>(g16), S(stream)),
           "lamb_bf16");
   }, "lamb reading the bf16 (wire-format) gradient");
   m.def("lamb_partials", [](size_t n, uintptr_t ranges, int n_ranges) {

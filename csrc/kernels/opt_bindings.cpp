@@ -1,32 +1,9 @@
-// pybind11 bindings of optim.hip (module `_dgopt`): SGD with momentum, Nesterov and weight
-// decay.  Its own extension, imported only for optimizer=momentum, so the interface of `_dghip`
-// stays as recorded.  Conventions as in bindings.cpp: tensors cross as raw device addresses,
-// the range table as the address of a host int64 array, the stream as its handle; a launcher's
-// error becomes RuntimeError("<name>: <hipGetErrorString>").  dg_api.h declares dg_momentum.
-// optim.hip also holds AdamW (dg_adamw); that is bound in adam_bindings.cpp (module `_dgadam`),
-// because this module's public names are pinned to the two below.
-#include <pybind11/pybind11.h>
-
-#include <stdexcept>
-#include <string>
-
-#include "dg_api.h"
-
-namespace py = pybind11;
-
-namespace {
-
-template <typename T>
-T* P(uintptr_t v) {
-  return reinterpret_cast<T*>(v);
-}
-
-void check(hipError_t e, const char* what) {
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-}  // namespace
+// pybind11 bindings of optim.hip's momentum (module `_dgopt`): SGD with momentum, Nesterov and
+// weight decay.  Its own extension, imported only for optimizer=momentum; its public names are
+// pinned to the two below, so optim.hip's AdamW and LAMB are bound in modules of their own
+// (adam_bindings.cpp, lamb_bindings.cpp).  dg_api.h declares dg_momentum; dg_bind.h says how it
+// crosses the boundary (the range table is the address of a host int64 array).
+#include "dg_bind.h"
 
 PYBIND11_MODULE(_dgopt, m) {
   m.doc() = "deep_go_amd SGD with momentum / Nesterov / weight decay (gfx950)";
@@ -34,8 +11,7 @@ PYBIND11_MODULE(_dgopt, m) {
                        int nesterov, float wd, uintptr_t ranges, int n_ranges, float gscale,
                        uintptr_t gate, uintptr_t stream) {
     check(dg_momentum(P<float>(p), P<float>(g), P<float>(v), n, P<double>(lr), mu, nesterov, wd,
-                      P<long long>(ranges), n_ranges, gscale, P<float>(gate), nullptr,
-                      reinterpret_cast<hipStream_t>(stream)),
+                      P<long long>(ranges), n_ranges, gscale, P<float>(gate), nullptr, S(stream)),
           "momentum");
   }, "v = mu v + (g gscale + wd p [in ranges]); p -= lr (nesterov ? gw + mu v : v)");
   m.def("momentum_bf16", [](uintptr_t p, uintptr_t g16, uintptr_t v, size_t n, uintptr_t lr,
@@ -43,7 +19,7 @@ PYBIND11_MODULE(_dgopt, m) {
                             float gscale, uintptr_t gate, uintptr_t stream) {
     check(dg_momentum(P<float>(p), nullptr, P<float>(v), n, P<double>(lr), mu, nesterov, wd,
                       P<long long>(ranges), n_ranges, gscale, P<float>(gate), P<void>(g16),
-                      reinterpret_cast<hipStream_t>(stream)),
+                      S(stream)),
           "momentum_bf16");
   }, "momentum reading the bf16 (wire-format) gradient");
 }

@@ -1,9 +1,8 @@
 // The optimizers with a launch of their own over the flat fp32 master vector: SGD with momentum,
-// Nesterov and weight decay (dg_momentum: module _dgopt, opt_bindings.cpp, loaded only for
-// optimizer=momentum) and AdamW (dg_adamw, further down: module _dgadam, adam_bindings.cpp,
-// loaded only for optimizer=adamw) and LAMB (dg_lamb, last: module _dglamb, lamb_bindings.cpp,
-// loaded only for optimizer=lamb).  None is part of _dghip, so its interface stays as
-// recorded.  deep_go_amd/train/optim.py Momentum is the definition; per element i
+// Nesterov and weight decay (dg_momentum: module _dgopt), AdamW (dg_adamw, further down: module
+// _dgadam) and LAMB (dg_lamb, last: module _dglamb).  This file is compiled once and linked into
+// all three; each module has its own <name>_bindings.cpp and is loaded only for its optimizer=
+// setting.  deep_go_amd/train/optim.py Momentum is the definition; per element i
 //
 //   gi = g[i] * gscale
 //   gw = gi + wd * p[i]          if i lies in a decay range (the conv weights), else gi
@@ -37,18 +36,9 @@ struct DecayRanges {
   unsigned e[MAX_RANGES];
 };
 
-// as elementwise.hip: gradient 4-vector i4 from the flat fp32 gradient (16-byte load) or from
-// its bf16 wire twin (8-byte load).  The raw bits are loaded first and widened only where the
-// update needs them, so the wait for the load comes after the mask is found.
-DG_DEV float grad_at(const float* g, size_t i) { return g[i]; }
-DG_DEV float grad_at(const bf16_t* g, size_t i) { return bf2f(g[i]); }
-DG_DEV f32x4 grad4_raw(const float* g, size_t i4) { return ((const f32x4*)g)[i4]; }
-DG_DEV uint2 grad4_raw(const bf16_t* g, size_t i4) { return ((const uint2*)g)[i4]; }
-DG_DEV f32x4 grad4_f32(const f32x4 raw) { return raw; }
-DG_DEV f32x4 grad4_f32(const uint2 u) {
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-               __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u)};
-}
+// The gradient is read with grad4_raw / grad4_f32 (dg_common.h): the raw bits are loaded first
+// and widened only where the update needs them, so the wait for the load comes after the mask is
+// found.
 
 // The decay mask of one workgroup pass: MT consecutive 4-vectors from 4-vector c0, thread tid's
 // four elements -> `in` inside a decay range, 0 elsewhere.  The chunk's position is uniform,
@@ -301,12 +291,6 @@ DG_DEV void chunk_span(const DecayRanges& R, int q, unsigned e0, unsigned e1, in
   hi = R.e[q] < e1 ? (int)(R.e[q] - e0) : CE;
 }
 
-DG_DEV double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one element: m, v as adamw_update; -> u without the decay term
 DG_DEV float lamb_update(float& m, float& v, float g, float c1, float b1, float o1, float b2,
                          float o2, float c2, float eps, float gscale) {
@@ -426,8 +410,8 @@ lamb_ratio(const float* __restrict__ part, size_t n, const DecayRanges R,
       su += (double)pr.y;
     }
   }
-  sp = wave_sum_d(sp);
-  su = wave_sum_d(su);
+  sp = wave_sum_f64(sp);
+  su = wave_sum_f64(su);
   if ((tid & 63) == 0) s_w[0][tid >> 6] = sp, s_w[1][tid >> 6] = su;
   __syncthreads();
   if (tid != 0) return;

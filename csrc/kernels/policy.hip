@@ -3,8 +3,7 @@
 // from the head's log-probabilities (policy_ensemble).  deep_go_amd/data/symmetry.py holds the
 // definition of the symmetries and the float64 oracle of policy_ensemble.
 //
-// A point is p = 19 x + y.  For s in 0..7, T_s maps (x, y): if s & 4 first swap to (y, x), then
-// apply (a, b) -> (b, 18 - a) exactly s & 3 times.  s = 0 is the identity.
+// The symmetries T_s, s in 0..7, of a point p = 19 x + y are sym_fwd / sym_inv of dg_common.h.
 //
 // Plain C++ with wave shuffles: no atomics, every reduction in a fixed order, so the results
 // are bit-reproducible from run to run.
@@ -19,22 +18,6 @@ constexpr int PLANES = 9;      // stored uint8 planes per position (data/feature
 constexpr int PT = 256;        // threads per workgroup of both kernels
 constexpr int PW = PT / 64;    // waves per workgroup
 constexpr int MAX_TOPK = 64;
-
-// T_s(p)
-DG_DEV int sym_fwd(int s, int p) {
-  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
-  if (s & 4) { const int t = a; a = b; b = t; }
-  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = b; b = BOARD - 1 - t; }
-  return a * BOARD + b;
-}
-
-// T_s^-1(p): undo the rotations ((a, b) -> (18 - b, a)), then the swap
-DG_DEV int sym_inv(int s, int p) {
-  int a = p / BOARD, b = p - (p / BOARD) * BOARD;
-  for (int r = 0; r < (s & 3); ++r) { const int t = a; a = BOARD - 1 - b; b = t; }
-  if (s & 4) { const int t = a; a = b; b = t; }
-  return a * BOARD + b;
-}
 
 // ------------------------------------------------------------------------------------
 // Destination board j = i S + s of a packed batch <- source board i moved by T_s: the nine

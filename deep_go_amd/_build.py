@@ -1,19 +1,15 @@
 """In-tree native build: hipcc for the gfx950 kernels, g++ for the CPU engine.
 
-Produces ``deep_go_amd/_native/_dghip<EXT>`` (HIP kernels, pybind11),
-``deep_go_amd/_native/_dgaug<EXT>`` (the batch-augmentation kernel, its own small module),
-``deep_go_amd/_native/_dgopt<EXT>`` (the momentum optimizer's kernel, likewise),
-``deep_go_amd/_native/_dgadam<EXT>`` (the AdamW optimizer's kernels: the same optim.hip behind
-bindings of its own),
-``deep_go_amd/_native/_dglamb<EXT>`` (the LAMB optimizer's kernels: optim.hip again),
-``deep_go_amd/_native/_dgclip<EXT>`` (gradient clipping by the global norm: clip.hip),
-``deep_go_amd/_native/_dgema<EXT>`` (the moving average of the weights: ema.hip),
-``deep_go_amd/_native/_dgsched<EXT>`` (the learning-rate schedule: sched.hip) and
-``deep_go_amd/_native/_dgcpu<EXT>`` (Go engine, t7 codec, SGF parser, loader thread
-pool).  Built in-tree so the ``.so`` files travel with the repo snapshot to the GPU box.
+Produces, under ``deep_go_amd/_native/`` (in-tree, so the ``.so`` files travel with the tree):
 
-Usage: ``python -m deep_go_amd._build [--force] [--only
-hip|aug|opt|adam|lamb|clip|ema|sched|cpu|comm]
+* ``_dghip<EXT>``: the HIP kernels of the network (``HIP_SOURCES``), pybind11;
+* ``_dg<name><EXT>`` for every row of ``SMALL``: one kernel file and its bindings each, apart
+  from ``_dghip`` and from one another because the interface of each is recorded or pinned by
+  tests, and imported only when the feature is asked for;
+* ``_dgcpu<EXT>``: Go engine, t7 codec, SGF parser, loader thread pool;
+* ``_dgcomm<EXT>``: the native RCCL communicator.
+
+Usage: ``python -m deep_go_amd._build [--force] [--only hip|<a name of SMALL>|cpu|comm]
 [--sanitize thread|address]``
 """
 from __future__ import annotations
@@ -42,6 +38,17 @@ HIP_SOURCES = ["conv_mfma.hip", "conv_board.hip", "conv_stack2.hip", "conv_layer
 # the kernels' compile flags (tools/kloop_report.py compiles with the same ones)
 HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
              "-Wno-unused-result"]
+# the small modules _dg<name>: name -> (kernel file, bindings file).  ops/native.py's accessors
+# and __graft_entry__.build() go by this table too.
+SMALL = {
+    "aug": ("augment.hip", "aug_bindings.cpp"),     # on-device D4 batch augmentation
+    "opt": ("optim.hip", "opt_bindings.cpp"),       # SGD with momentum / Nesterov / weight decay
+    "adam": ("optim.hip", "adam_bindings.cpp"),     # AdamW
+    "lamb": ("optim.hip", "lamb_bindings.cpp"),     # LAMB
+    "clip": ("clip.hip", "clip_bindings.cpp"),      # gradient clipping by the global norm
+    "ema": ("ema.hip", "ema_bindings.cpp"),         # the moving average of the weights
+    "sched": ("sched.hip", "sched_bindings.cpp"),   # the learning-rate schedule's launch
+}
 CPU_SOURCES = ["go_engine.cpp", "sgf.cpp", "t7.cpp", "features.cpp", "loader.cpp",
                "bindings.cpp"]
 
@@ -65,96 +72,48 @@ def _run(cmd):
     return r
 
 
-def build_hip(force: bool = False, jobs: int = 8) -> Path:
+def _objects(prefix: str, sources, force: bool, jobs: int) -> list[Path]:
+    """build/<prefix>_<source>.o of each of KDIR's sources (.hip: device code with HIP_FLAGS,
+    .cpp: pybind11 host code), the stale ones compiled in a thread pool."""
     BUILD.mkdir(exist_ok=True)
-    OUT.mkdir(exist_ok=True)
-    target = OUT / f"_dghip{EXT}"
     headers = list(KDIR.glob("*.h"))
     objs, cmds = [], []
-    for s in HIP_SOURCES:
-        src = KDIR / s
-        if not src.exists():
-            continue
-        obj = BUILD / ("hip_" + s + ".o")
+    for s in sources:
+        src, obj = KDIR / s, BUILD / f"{prefix}_{s}.o"
         objs.append(obj)
         if force or _newer(src, obj, headers):
-            cmd = [HIPCC, *HIP_FLAGS, "-c", str(src), "-o", str(obj)]
-            if s.endswith(".cpp"):
-                cmd = [HIPCC, "-O2", "-std=c++17", "-fPIC", *(_pybind_includes()), "-c",
-                       str(src), "-o", str(obj)]
-            cmds.append(cmd)
+            flags = HIP_FLAGS if s.endswith(".hip") else ["-O2", "-std=c++17", "-fPIC",
+                                                          *_pybind_includes()]
+            cmds.append([HIPCC, *flags, "-c", str(src), "-o", str(obj)])
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         list(ex.map(_run, cmds))
-    if force or cmds or not target.exists():
+    return objs
+
+
+def _link(name: str, objs, force: bool) -> Path:
+    """_native/_dg<name><EXT> from the objects, when one of them is newer than it."""
+    OUT.mkdir(exist_ok=True)
+    target = OUT / f"_dg{name}{EXT}"
+    if force or any(_newer(o, target) for o in objs):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "--hip-link", "-o",
               str(target), *map(str, objs)])
     return target
 
 
-def _build_small(name: str, kernel: str, binding: str, force: bool) -> Path:
-    """A module of one kernel file and its bindings (objects build/<name>_<source>.o)."""
-    BUILD.mkdir(exist_ok=True)
-    OUT.mkdir(exist_ok=True)
-    target = OUT / f"_dg{name}{EXT}"
-    headers = list(KDIR.glob("*.h"))
-    kern, kobj = KDIR / kernel, BUILD / f"{name}_{kernel}.o"
-    bind, bobj = KDIR / binding, BUILD / f"{name}_{binding}.o"
-    built = False
-    if force or _newer(kern, kobj, headers):
-        _run([HIPCC, *HIP_FLAGS, "-c", str(kern), "-o", str(kobj)])
-        built = True
-    if force or _newer(bind, bobj, headers):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", *(_pybind_includes()), "-c", str(bind), "-o",
-              str(bobj)])
-        built = True
-    if force or built or not target.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "--hip-link", "-o",
-              str(target), str(kobj), str(bobj)])
-    return target
+def build_hip(force: bool = False, jobs: int = 8) -> Path:
+    return _link("hip", _objects("hip", HIP_SOURCES, force, jobs), force)
 
 
-def build_aug(force: bool = False) -> Path:
-    """_dgaug: the training-time symmetry augmentation (augment.hip + its two bindings), apart
-    from _dghip so that module's recorded interface stays as it is."""
-    return _build_small("aug", "augment.hip", "aug_bindings.cpp", force)
+def build_smalls(names, force: bool = False, jobs: int = 8) -> list[Path]:
+    """The small modules named: every distinct source is compiled once (optim.hip is in three
+    modules) and its object linked into each module that lists it."""
+    sources = sorted({s for n in names for s in SMALL[n]})
+    obj = dict(zip(sources, _objects("small", sources, force, jobs)))
+    return [_link(n, [obj[s] for s in SMALL[n]], force) for n in names]
 
 
-def build_opt(force: bool = False) -> Path:
-    """_dgopt: SGD with momentum / Nesterov / weight decay (optim.hip + its two bindings),
-    apart from _dghip for the same reason."""
-    return _build_small("opt", "optim.hip", "opt_bindings.cpp", force)
-
-
-def build_adam(force: bool = False) -> Path:
-    """_dgadam: AdamW (optim.hip, where it shares the decay ranges and gradient loads with
-    momentum, + adam_bindings.cpp).  A module of its own: the public names of _dgopt are
-    pinned by its tests."""
-    return _build_small("adam", "optim.hip", "adam_bindings.cpp", force)
-
-
-def build_lamb(force: bool = False) -> Path:
-    """_dglamb: LAMB (optim.hip, where it shares the range table, the chunk lookup, the gradient
-    loads and the count's launch with AdamW, + lamb_bindings.cpp).  A module of its own: the
-    public names of _dgopt and _dgadam are pinned by their tests."""
-    return _build_small("lamb", "optim.hip", "lamb_bindings.cpp", force)
-
-
-def build_clip(force: bool = False) -> Path:
-    """_dgclip: global-norm gradient clipping (clip.hip + clip_bindings.cpp), imported only for
-    grad_clip > 0 and apart from the other modules, whose interfaces are recorded or pinned."""
-    return _build_small("clip", "clip.hip", "clip_bindings.cpp", force)
-
-
-def build_ema(force: bool = False) -> Path:
-    """_dgema: the exponential moving average of the weights (ema.hip + ema_bindings.cpp),
-    imported only for ema_decay > 0 and apart from the other modules for the same reason."""
-    return _build_small("ema", "ema.hip", "ema_bindings.cpp", force)
-
-
-def build_sched(force: bool = False) -> Path:
-    """_dgsched: the learning-rate schedule's launch (sched.hip + sched_bindings.cpp), imported
-    only for lr_schedule != none and apart from the other modules for the same reason."""
-    return _build_small("sched", "sched.hip", "sched_bindings.cpp", force)
+def build_small(name: str, force: bool = False) -> Path:
+    return build_smalls([name], force)[0]
 
 
 def build_cpu(force: bool = False, jobs: int = 8, sanitize: str | None = None) -> Path:
@@ -209,43 +168,30 @@ def build_comm(force: bool = False) -> Path:
 def build_all(force: bool = False) -> None:
     build_cpu(force)
     build_hip(force)
-    build_aug(force)
-    build_opt(force)
-    build_adam(force)
-    build_lamb(force)
-    build_clip(force)
-    build_ema(force)
-    build_sched(force)
+    build_smalls(SMALL, force)
     build_comm(force)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
-    ap.add_argument("--only", choices=["hip", "aug", "opt", "adam", "lamb", "clip", "ema", "sched",
-                                       "cpu", "comm"])
+    ap.add_argument("--only", choices=["hip", *SMALL, "cpu", "comm"])
     ap.add_argument("--sanitize", choices=["thread", "address", "address,undefined"])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 4))
     a = ap.parse_args(argv)
-    if a.only in (None, "cpu"):
+
+    def wanted(name):
+        return a.only in (None, name)
+
+    if wanted("cpu"):
         print(build_cpu(a.force, a.j, a.sanitize))
-    if a.only in (None, "hip") and not a.sanitize:
+    if a.sanitize:
+        return
+    if wanted("hip"):
         print(build_hip(a.force, a.j))
-    if a.only in (None, "aug") and not a.sanitize:
-        print(build_aug(a.force))
-    if a.only in (None, "opt") and not a.sanitize:
-        print(build_opt(a.force))
-    if a.only in (None, "adam") and not a.sanitize:
-        print(build_adam(a.force))
-    if a.only in (None, "lamb") and not a.sanitize:
-        print(build_lamb(a.force))
-    if a.only in (None, "clip") and not a.sanitize:
-        print(build_clip(a.force))
-    if a.only in (None, "ema") and not a.sanitize:
-        print(build_ema(a.force))
-    if a.only in (None, "sched") and not a.sanitize:
-        print(build_sched(a.force))
-    if a.only in (None, "comm") and not a.sanitize:
+    for target in build_smalls([n for n in SMALL if wanted(n)], a.force, a.j):
+        print(target)
+    if wanted("comm"):
         print(build_comm(a.force))
 
 

@@ -1,18 +1,13 @@
-"""Loading of the in-tree native extensions.
+"""Loading of the in-tree native extensions, each on first use.
 
-``hip()`` returns the ``_dghip`` module (CDNA4 kernels); ``aug()`` the small ``_dgaug`` module
-(the batch-augmentation kernel), imported only when augmentation is asked for; ``opt()`` the
-``_dgopt`` module (the momentum optimizer's kernel), imported only for it; ``adam()`` the
-``_dgadam`` module (the AdamW optimizer's kernels), likewise; ``lamb()`` the ``_dglamb`` module
-(the LAMB optimizer's kernels), likewise; ``clip()`` the ``_dgclip`` module
-(gradient clipping by the global norm), imported only for ``grad_clip > 0``; ``ema()`` the
-``_dgema`` module (the moving average of the weights), imported only for ``ema_decay > 0``;
-``sched()`` the ``_dgsched`` module (the learning-rate schedule's launch), imported only for
-``lr_schedule != none``.  On a machine
-with a GPU a missing or stale extension is a hard error — there is deliberately no silent
-PyTorch fallback for the GPU compute path.  ``cpu()`` returns ``_dgcpu`` (Go engine, t7 codec,
-SGF parser, loader thread pool).  All are built by ``python -m deep_go_amd._build``
-(also run by ``__graft_entry__.build()``); set ``DG_AUTOBUILD=1`` to build on first use.
+One accessor per module: ``hip()`` returns ``_dghip`` (the CDNA4 kernels of the network),
+``cpu()`` ``_dgcpu`` (Go engine, t7 codec, SGF parser, loader thread pool), ``comm()``
+``_dgcomm`` (the RCCL communicator), and ``aug()``, ``opt()``, ``adam()``, ``lamb()``,
+``clip()``, ``ema()``, ``sched()`` the small ``_dg<name>`` modules of ``_build.SMALL``, which
+only the feature that needs one imports.  On a machine with a GPU a missing or stale extension
+is a hard error: there is deliberately no silent PyTorch fallback for the GPU compute path.
+All are built by ``python -m deep_go_amd._build`` (also run by ``__graft_entry__.build()``);
+set ``DG_AUTOBUILD=1`` to build on first use.
 """
 from __future__ import annotations
 
@@ -41,13 +36,11 @@ def _load(name: str):
     except ImportError as e:
         if os.environ.get("DG_AUTOBUILD", "0") == "1":
             from .. import _build
-            {"_dghip": _build.build_hip, "_dgaug": _build.build_aug,
-             "_dgopt": _build.build_opt, "_dgadam": _build.build_adam,
-             "_dglamb": _build.build_lamb,
-             "_dgclip": _build.build_clip, "_dgema": _build.build_ema,
-             "_dgsched": _build.build_sched,
-             "_dgcomm": _build.build_comm}.get(
-                name, _build.build_cpu)()
+            if name[3:] in _build.SMALL:
+                _build.build_small(name[3:])
+            else:
+                {"_dghip": _build.build_hip, "_dgcomm": _build.build_comm}.get(
+                    name, _build.build_cpu)()
             mod = importlib.import_module(name)
         else:
             raise NativeExtensionMissing(

@@ -13,6 +13,12 @@ calls the real functions.  These tests close the gap between the two on the CPU:
   ``python tests/test_native_api_cpu.py --write device_sync last_error``
   (names after ``--write`` are left out: that change removed these two, which nothing
   called).  Regenerate only for an intended change of the interface.
+* ``tests/fixtures/native_signatures_small.json`` does the same for the seven small modules
+  (``_dgaug``, ``_dgopt``, ``_dgadam``, ``_dglamb``, ``_dgclip``, ``_dgema``, ``_dgsched``), with
+  the full ``__doc__`` of every public name and of the module itself (key ``__doc__``).  It was
+  recorded from their hand-written bindings, at the commit before they moved to the shared
+  adapter of ``csrc/kernels/dg_bind.h``, with
+  ``python tests/test_native_api_cpu.py --write-small``.
 * every call recorded in ``tests/fixtures/launch_traces.json`` fits the signature of the
   function it names: the argument count, no ``float`` at an integer position, and pointers
   (symbolised buffers, tables, streams) only at integer positions.
@@ -34,6 +40,8 @@ if ROOT not in sys.path:
 from deep_go_amd.ops import native  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "fixtures", "native_signatures.json")
+FIXTURE_SMALL = os.path.join(ROOT, "tests", "fixtures", "native_signatures_small.json")
+SMALL = ("aug", "opt", "adam", "lamb", "clip", "ema", "sched")      # native.<name>() -> _dg<name>
 TRACES = os.path.join(ROOT, "tests", "fixtures", "launch_traces.json")
 
 # trace entries that are not native calls (the fakes of tests/test_launch_trace_cpu.py)
@@ -49,6 +57,16 @@ def _interface(mod):
             continue
         v = getattr(mod, name)
         out[name] = v if isinstance(v, int) else v.__doc__.splitlines()[0]
+    return out
+
+
+def _interface_full(mod):
+    """{public name: full pybind doc | value (int attributes)} + the module's own __doc__."""
+    out = {"__doc__": mod.__doc__}
+    for name in dir(mod):
+        if not name.startswith("_"):
+            v = getattr(mod, name)
+            out[name] = v if isinstance(v, int) else v.__doc__
     return out
 
 
@@ -84,6 +102,20 @@ def test_module_matches_recorded_interface(h, recorded):
     assert sorted(got) == sorted(recorded)
     for name, want in recorded.items():
         assert got[name] == want, name
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_small_module_matches_recorded_interface(name):
+    try:
+        mod = getattr(native, name)()
+    except native.NativeExtensionMissing:
+        pytest.skip(f"_dg{name} is not built")
+    with open(FIXTURE_SMALL) as f:
+        want = json.load(f)["_dg" + name]
+    got = _interface_full(mod)
+    assert sorted(got) == sorted(want)
+    for k, v in want.items():
+        assert got[k] == v, k
 
 
 def test_recorded_launches_fit_the_signatures(recorded):
@@ -135,8 +167,15 @@ def test_queries_return_values(h):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--write-small"]:
+        small = {"_dg" + n: _interface_full(getattr(native, n)()) for n in SMALL}
+        with open(FIXTURE_SMALL, "w") as f:
+            json.dump(small, f, indent=0, sort_keys=True)
+            f.write("\n")
+        sys.exit(print(f"{len(small)} modules -> {FIXTURE_SMALL}"))
     if sys.argv[1:2] != ["--write"]:
-        sys.exit("usage: python tests/test_native_api_cpu.py --write [NAME_TO_LEAVE_OUT ...]")
+        sys.exit("usage: python tests/test_native_api_cpu.py --write [NAME_TO_LEAVE_OUT ...]\n"
+                 "       python tests/test_native_api_cpu.py --write-small")
     iface = {k: v for k, v in _interface(native.hip()).items() if k not in sys.argv[2:]}
     with open(FIXTURE, "w") as f:
         json.dump(iface, f, indent=0, sort_keys=True)
