@@ -494,6 +494,60 @@ PYBIND11_MODULE(_dgcpu, m) {
     return py::make_tuple(P, PL, RK, LB);
   });
 
+  py::class_<Game>(m, "Game",
+                   "a live game: Board, side to move and history (points are p = 19 x + y)")
+      .def(py::init<>())
+      .def("clear", &Game::clear)
+      .def("play", &Game::play, py::arg("player"), py::arg("x"), py::arg("y"),
+           "a stone of player (1 black, 2 white) at 0-based (x, y); raises on an occupied point")
+      .def("pass_", &Game::pass_, py::arg("player"),
+           "player passes: the ko point is cleared, ages advance as for a move")
+      .def("undo", &Game::undo,
+           "take back the last play / pass_ exactly; False at the start of the game")
+      .def_property_readonly("to_move", &Game::to_move)
+      .def_property_readonly("ply", &Game::ply)
+      .def_property_readonly("last_was_pass", &Game::last_was_pass)
+      .def("stones",
+           [](const Game& g) {
+             py::array_t<uint8_t> out({19, 19});
+             std::memcpy(out.mutable_data(), g.board().stones().data(), NN);
+             return out;
+           })
+      .def("ages",
+           [](const Game& g) {
+             py::array_t<uint8_t> out({19, 19});
+             std::memcpy(out.mutable_data(), g.board().ages().data(), NN);
+             return out;
+           })
+      .def("ko", &Game::ko, "the simple-ko point (19 x + y, -1 none)")
+      .def("key", &Game::key, "the 64-bit Zobrist key of the stones")
+      .def("planes",
+           [](Game& g, bool mark_ko) {
+             py::array_t<uint8_t> out({9, 19, 19});
+             g.planes(out.mutable_data(), mark_ko);
+             return out;
+           },
+           py::arg("mark_ko") = false,
+           "the stored planes [9,19,19] of the current position (game_positions' row k after "
+           "k moves)")
+      .def("legal_mask",
+           [](Game& g, int player, bool suicide, bool superko, bool eye_fill) {
+             py::array_t<uint8_t> out((py::ssize_t)NN);
+             g.legal_mask(player, suicide, superko, eye_fill, out.mutable_data());
+             return out;
+           },
+           py::arg("player"), py::arg("suicide") = false, py::arg("superko") = true,
+           py::arg("eye_fill") = true,
+           "uint8 [361], nonzero = illegal: occupied, the simple-ko point, suicide (unless "
+           "suicide), positional-superko repeats (superko), own simple eyes (unless eye_fill)")
+      .def("score",
+           [](const Game& g) {
+             int b = 0, w = 0;
+             g.score(&b, &w);
+             return py::make_tuple(b, w);
+           },
+           "Tromp-Taylor (black_area, white_area)");
+
   py::class_<PyLoader>(m, "Loader")
       .def(py::init<const std::vector<std::tuple<std::string, int64_t, int>>&, int, int,
                     const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t>>&,

@@ -28,7 +28,31 @@ struct NbrInit {
 } g_nbr_init;
 
 constexpr long long kLadderNodeCap = 50000000;  // never reached on real games
+
+// Zobrist table: splitmix64 from a fixed seed, in the order (colour 1, colour 2) x point
+uint64_t g_zobrist[2][NN];
+struct ZobristInit {
+  ZobristInit() {
+    uint64_t state = 0x64675f676f5f7a6bull;
+    for (auto& colour : g_zobrist)
+      for (uint64_t& k : colour) {
+        uint64_t z = (state += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        k = z ^ (z >> 31);
+      }
+  }
+} g_zobrist_init;
 }  // namespace
+
+uint64_t zobrist(int colour, int idx) { return g_zobrist[colour - 1][idx]; }
+
+uint64_t position_key(const std::array<uint8_t, NN>& stones) {
+  uint64_t k = 0;
+  for (int i = 0; i < NN; ++i)
+    if (stones[i]) k ^= g_zobrist[stones[i] - 1][i];
+  return k;
+}
 
 Board::Board() { clear(); }
 
@@ -146,6 +170,32 @@ void Board::kills_and_liberties(int idx, int player, int* kills, int* libs_after
   unwind(log, 0);
 }
 
+uint64_t Board::trial_key_delta(int idx, int player, int* kills, int* libs_after) {
+  std::vector<Undo> log;
+  int k = 0;
+  place_and_resolve(idx, player, &log, &k, nullptr);
+  *libs_after = liberties(idx);
+  *kills = k;
+  // the log's first entry is the stone placed on the empty point; every later one clears a stone
+  uint64_t delta = zobrist(player, idx);
+  for (size_t i = 1; i < log.size(); ++i) delta ^= zobrist(log[i].prev, log[i].idx);
+  unwind(log, 0);
+  return delta;
+}
+
+void Board::pass() {
+  for (int i = 0; i < NN; ++i)
+    if (age_[i] > 0 && age_[i] < 255) ++age_[i];
+  ko_ = -1;
+}
+
+void Board::restore(const std::array<uint8_t, NN>& stones, const std::array<uint8_t, NN>& ages,
+                    int ko) {
+  s_ = stones;
+  age_ = ages;
+  ko_ = ko;
+}
+
 bool Board::ladder_moves(int gx, const int libs2[2], std::vector<int>* result, int depth) {
   const int player = s_[gx];
   const int opp = 3 - player;
@@ -229,6 +279,106 @@ int game_positions(const std::vector<Move>& handicap, const std::vector<Move>& m
     ++k;
   }
   return k;
+}
+
+// ------------------------------------------------------------------------------ Game
+Game::Game() { clear(); }
+
+void Game::clear() {
+  b_.clear();
+  to_move_ = 1;
+  hist_.clear();
+  keys_.assign(1, 0);
+}
+
+void Game::play(int player, int x, int y) {
+  if (player != 1 && player != 2) throw IllegalMove("player must be 1 or 2");
+  Entry e{b_.stones(), b_.ages(), b_.ko(), to_move_, false};
+  b_.play({player, x, y});   // throws before it changes anything
+  hist_.push_back(e);
+  keys_.push_back(position_key(b_.stones()));
+  to_move_ = 3 - player;
+}
+
+void Game::pass_(int player) {
+  if (player != 1 && player != 2) throw IllegalMove("player must be 1 or 2");
+  hist_.push_back({b_.stones(), b_.ages(), b_.ko(), to_move_, true});
+  b_.pass();
+  keys_.push_back(keys_.back());
+  to_move_ = 3 - player;
+}
+
+bool Game::undo() {
+  if (hist_.empty()) return false;
+  const Entry& e = hist_.back();
+  b_.restore(e.stones, e.ages, e.ko);
+  to_move_ = e.to_move;
+  hist_.pop_back();
+  keys_.pop_back();
+  return true;
+}
+
+bool Game::simple_eye(int idx, int player) const {
+  if (b_.at(idx) != 0) return false;
+  for (int k = 0; k < g_nnbr[idx]; ++k)
+    if (b_.at(g_nbr[idx][k]) != player) return false;
+  const int x = idx / N, y = idx % N;
+  int on_board = 0, not_own = 0;
+  for (int dx = -1; dx <= 1; dx += 2)
+    for (int dy = -1; dy <= 1; dy += 2) {
+      const int a = x + dx, b = y + dy;
+      if (a < 0 || a >= N || b < 0 || b >= N) continue;
+      ++on_board;
+      if (b_.at(a * N + b) != player) ++not_own;
+    }
+  return not_own <= (on_board == 4 ? 1 : 0);
+}
+
+void Game::legal_mask(int player, bool suicide, bool superko, bool eye_fill, uint8_t* out) {
+  if (player != 1 && player != 2) throw IllegalMove("player must be 1 or 2");
+  for (int i = 0; i < NN; ++i) {
+    out[i] = 1;
+    if (b_.at(i) != 0 || i == b_.ko()) continue;
+    if (!eye_fill && simple_eye(i, player)) continue;
+    int kills = 0, libs = 0;
+    const uint64_t after = keys_.back() ^ b_.trial_key_delta(i, player, &kills, &libs);
+    if (!suicide && kills == 0 && libs == 0) continue;
+    if (superko && std::find(keys_.begin(), keys_.end(), after) != keys_.end()) continue;
+    out[i] = 0;
+  }
+}
+
+void Game::score(int* black, int* white) const {
+  int area[3] = {0, 0, 0};
+  std::array<uint8_t, NN> seen{};
+  std::vector<int> stack;
+  for (int i = 0; i < NN; ++i) {
+    if (b_.at(i) != 0) {
+      ++area[b_.at(i)];
+      continue;
+    }
+    if (seen[i]) continue;
+    int size = 0, reach = 0;   // reach: bit 1 black, bit 2 white
+    seen[i] = 1;
+    stack.assign(1, i);
+    while (!stack.empty()) {
+      const int h = stack.back();
+      stack.pop_back();
+      ++size;
+      for (int k = 0; k < g_nnbr[h]; ++k) {
+        const int n = g_nbr[h][k];
+        if (b_.at(n) != 0) {
+          reach |= b_.at(n);
+        } else if (!seen[n]) {
+          seen[n] = 1;
+          stack.push_back(n);
+        }
+      }
+    }
+    if (reach == 1 || reach == 2) area[reach] += size;
+  }
+  *black = area[1];
+  *white = area[2];
 }
 
 }  // namespace dg

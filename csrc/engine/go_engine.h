@@ -78,6 +78,16 @@ class Board {
   // (age plane = current ages; mark_ko: KO_MARK in the liberty plane at the ko point).
   void summarize(uint8_t* out, bool mark_ko = false);
 
+  // Trial play of `player` at empty idx as kills_and_liberties, returning also the XOR of the
+  // Zobrist keys (position_key) of the position after the play and the position now.
+  uint64_t trial_key_delta(int idx, int player, int* kills, int* libs_after);
+
+  // A move that places no stone (Game::pass_): ages advance as for a move, no ko point.
+  void pass();
+  // Put back a position recorded from stones() / ages() / ko() (Game::undo).
+  void restore(const std::array<uint8_t, NN>& stones, const std::array<uint8_t, NN>& ages,
+               int ko);
+
   // Number of ladder-search nodes visited by the last summarize() (diagnostics).
   long long ladder_nodes() const { return ladder_nodes_; }
 
@@ -110,6 +120,65 @@ class Board {
 // mark_ko: each position's simple-ko point marked (Board::summarize).
 int game_positions(const std::vector<Move>& handicap, const std::vector<Move>& moves,
                    uint8_t* out, bool mark_ko = false);
+
+// Zobrist key of a stone of `colour` (1, 2) at idx: a fixed table filled at start-up by
+// splitmix64 from a fixed seed, so keys are the same in every process.  position_key: the XOR
+// over all stones (0 for the empty board); the side to move is not part of it.
+uint64_t zobrist(int colour, int idx);
+uint64_t position_key(const std::array<uint8_t, NN>& stones);
+
+// A live game: a Board, the side to move and the history of everything a move changes, so
+// undo() is exact.  Board's rules are unchanged (suicide is playable and ko is not enforced by
+// play()); what a player may do is legal_mask()'s business.
+class Game {
+ public:
+  Game();
+  void clear();
+  // A stone of `player` at (x, y), 0-based; throws IllegalMove on an occupied point or off the
+  // board.  The other colour is then to move.
+  void play(int player, int x, int y);
+  // `player` passes: the ko point is cleared and ages advance as for a move.
+  void pass_(int player);
+  // Take back the last play() / pass_(): stones, ages, ko, side to move and history bit for
+  // bit.  False (and no change) at the start of the game.
+  bool undo();
+
+  int to_move() const { return to_move_; }
+  int ply() const { return (int)hist_.size(); }
+  bool last_was_pass() const { return !hist_.empty() && hist_.back().was_pass; }
+  const Board& board() const { return b_; }
+  int ko() const { return b_.ko(); }
+  uint64_t key() const { return keys_.back(); }
+
+  // Board::summarize of the current position into out[9*361].
+  void planes(uint8_t* out, bool mark_ko = false) { b_.summarize(out, mark_ko); }
+
+  // out[361], nonzero = `player` may not play there.  Always: occupied points and the
+  // simple-ko point.  !suicide: points whose trial play kills nothing and leaves the played
+  // group without a liberty.  superko: points whose resulting position repeats an earlier
+  // position of this game, the current one included (positional superko, by Zobrist key).
+  // !eye_fill: the player's own simple eyes (simple_eye).
+  void legal_mask(int player, bool suicide, bool superko, bool eye_fill, uint8_t* out);
+
+  // An empty point whose on-board orthogonal neighbours are all `player`'s stones and of whose
+  // on-board diagonal neighbours at most one is not `player`'s stone (none on the edge or in a
+  // corner).
+  bool simple_eye(int idx, int player) const;
+
+  // Tromp-Taylor area: stones plus the empty regions that reach only that colour.
+  void score(int* black, int* white) const;
+
+ private:
+  struct Entry {   // the state before the move
+    std::array<uint8_t, NN> stones, ages;
+    int ko, to_move;
+    bool was_pass;
+  };
+  Board b_;
+  int to_move_ = 1;
+  std::vector<Entry> hist_;
+  std::vector<uint64_t> keys_;   // of the start position and of the position after every move
+};
 
 // Neighbour table in the reference's order: (-1,0), (1,0), (0,-1), (0,1).
 extern int g_nbr[NN][4];

@@ -21,17 +21,7 @@ constexpr int PLANES = 9;      // stored uint8 planes per position (data/feature
 constexpr int AT = 256;        // threads per workgroup
 constexpr int BOARD_BYTES = PLANES * NPTS;
 
-// the "lowbias32" finaliser
-__host__ __device__ inline uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// augment_symmetries of data/symmetry.py, one board
+// augment_symmetries of data/symmetry.py, one board (mix32: dg_common.h)
 __host__ __device__ inline int hash_symmetry(unsigned long long seed, unsigned long long seq,
                                              unsigned long long board) {
   const uint32_t a = mix32(((uint32_t)seed ^ 0x9e3779b9u) + (uint32_t)(seed >> 32));

@@ -315,6 +315,22 @@ hipError_t dg_augment_batch(uint8_t* planes, int* labels, int B, const uint8_t* 
 int dg_augment_symmetry(unsigned long long seed, unsigned long long seq,
                         unsigned long long board);
 
+// ---------------------------------------------------------------- play.hip (module _dgplay)
+// One move per position from policy_ensemble's prob [n][361] (masked and normalised), tempered
+// by `temperature` and cut to the top_p nucleus; the draw of position i is
+// dg_select_uniform(seed, game[i], ply[i]).  move [n]: the point, -1 for a row without a legal
+// point or with a non-finite or negative entry; p_move [n] (optional): the tempered,
+// renormalised probability of the chosen point; kept [n] (optional): the size of the nucleus (0
+// / -1 for those two kinds of row).  deep_go_amd/play/select.py is the definition.  Refused
+// before any GPU work: n < 0; a null prob, game, ply or move; temperature < 0 or not finite;
+// top_p outside (0, 1].
+hipError_t dg_policy_select(const float* prob, const int* game, const int* ply, int n,
+                            unsigned long long seed, float temperature, float top_p, int* move,
+                            float* p_move, int* kept, hipStream_t stream);
+// The draw behind it, on the host: u in [0, 1) on the 2^-24 grid (play/select.py
+// select_uniform is the definition).
+float dg_select_uniform(unsigned long long seed, int game, int ply);
+
 // ---------------------------------------- optim.hip (modules _dgopt, _dgadam and _dglamb)
 // SGD with momentum over the flat vector, one launch: gi = g * gscale; gw = gi + wd * p inside
 // a decay range, else gi; v = mu * v + gw; p -= lr * (nesterov ? gw + mu * v : v).  ranges: a

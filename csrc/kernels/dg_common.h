@@ -50,6 +50,17 @@ DG_DEV int sym_inv(int s, int p) {
   return a * BOARD + b;
 }
 
+// The "lowbias32" finaliser: the 32-bit mixing round of the stateless hashes (augment.hip's
+// symmetry draw, play.hip's select_uniform).  Host and device, so each has a host twin.
+__host__ __device__ inline uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
 // f32 -> bf16 round-to-nearest-even (NaN kept NaN via the compiler's v_cvt_pk_bf16_f32).
 DG_DEV bf16_t f2bf(float f) {
   __bf16 h = (__bf16)f;

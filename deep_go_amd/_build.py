@@ -48,6 +48,7 @@ SMALL = {
     "clip": ("clip.hip", "clip_bindings.cpp"),      # gradient clipping by the global norm
     "ema": ("ema.hip", "ema_bindings.cpp"),         # the moving average of the weights
     "sched": ("sched.hip", "sched_bindings.cpp"),   # the learning-rate schedule's launch
+    "play": ("play.hip", "play_bindings.cpp"),      # move selection: temperature, top-p, draw
 }
 CPU_SOURCES = ["go_engine.cpp", "sgf.cpp", "t7.cpp", "features.cpp", "loader.cpp",
                "bindings.cpp"]

@@ -13,6 +13,15 @@
   predict   CKPT GAME.sgf [--move N] [--top K] [--symmetries {1,8}] [--device auto|cpu|gpu] [--all]
             [--ema]
             (where to play and with what probability: one JSON line per requested move)
+  gtp       CKPT [--ema] [--device auto|cpu|gpu] [--symmetries {1,8}] [--temperature T] [--top-p P]
+            [--seed N] [--rank DAN] [--komi K]
+            (a GTP version 2 engine on stdin / stdout for Sabaki, GoGui or gogui-twogtp:
+            deep_go_amd.play.gtp)
+  selfplay  CKPT [--opponent CKPT2] --games N [--max-moves M] [--out DIR] [--komi K]
+            [--temperature T] [--top-p P] [--opening-plies K] [--seed N] [--rank DAN] [--batch B]
+            [--ema] [--device ...] [--symmetries {1,8}]
+            (lock-step batched self-play, or a match with colours alternating by game; one SGF
+            per game and summary.json into DIR, the summary also as one JSON line)
   makedata  scatter SRC DST train=N validation=N test=N | transcribe SRC DST [--threads T] [--ko]
             | count ROOT SPLIT | pack ROOT SPLIT
   export    CKPT OUT.t7 [--ema] (reference Torch7 experiment table)
@@ -184,6 +193,37 @@ def cmd_predict(args):
     return 0
 
 
+def _play_predictor(args, checkpoint, what, batch=64):
+    from .predict import Predictor
+    try:
+        return Predictor.load(checkpoint, ema=args.ema, symmetries=args.symmetries, top=1,
+                              device=args.device, batch=batch)
+    except ValueError as err:
+        if not args.ema:
+            raise
+        raise SystemExit(f"{what} --ema: {err}")
+
+
+def cmd_gtp(args):
+    from .play.gtp import GtpEngine
+    p = _play_predictor(args, args.checkpoint, "gtp", batch=args.symmetries)
+    GtpEngine(p, rank=args.rank, seed=args.seed, temperature=args.temperature,
+              top_p=args.top_p, komi=args.komi).run(sys.stdin, sys.stdout)
+    return 0
+
+
+def cmd_selfplay(args):
+    from .play.selfplay import run_match
+    a = _play_predictor(args, args.checkpoint, "selfplay", batch=args.batch)
+    b = _play_predictor(args, args.opponent, "selfplay", batch=args.batch) if args.opponent else None
+    r = run_match(a, b, games=args.games, max_moves=args.max_moves, komi=args.komi,
+                  rank=args.rank, seed=args.seed, temperature=args.temperature, top_p=args.top_p,
+                  opening_plies=args.opening_plies, out_dir=args.out)
+    # (the timing is printed only: summary.json depends on the arguments alone)
+    print(json.dumps({**r["summary"], "timing": r["timing"]}))
+    return 0
+
+
 def cmd_makedata(args):
     from .data import makedata as md
     a = args.rest
@@ -284,6 +324,27 @@ def main(argv=None):
     q.add_argument("--ema", action="store_true",
                    help="predict with the checkpoint's moving average of the weights")
     q.set_defaults(fn=cmd_predict)
+    for name, fn in (("gtp", cmd_gtp), ("selfplay", cmd_selfplay)):
+        g = sub.add_parser(name)
+        g.add_argument("checkpoint")
+        g.add_argument("--ema", action="store_true",
+                       help="play with the checkpoint's moving average of the weights")
+        g.add_argument("--device", choices=["auto", "cpu", "gpu"], default="auto")
+        g.add_argument("--symmetries", type=int, choices=[1, 8], default=8)
+        g.add_argument("--temperature", type=float, default=1.0)
+        g.add_argument("--top-p", type=float, default=1.0)
+        g.add_argument("--seed", type=int, default=0)
+        g.add_argument("--rank", type=int, default=9, help="the dan rank shown to the net")
+        g.add_argument("--komi", type=float, default=7.5)
+        if name == "selfplay":
+            g.add_argument("--opponent", help="a second checkpoint: a match, colours alternating")
+            g.add_argument("--games", type=int, required=True)
+            g.add_argument("--max-moves", type=int, default=400)
+            g.add_argument("--opening-plies", type=int, default=0,
+                           help="first plies drawn at temperature 1, top_p 1")
+            g.add_argument("--batch", type=int, default=64, help="boards per forward")
+            g.add_argument("--out", help="directory for the SGFs and summary.json")
+        g.set_defaults(fn=fn)
     m = sub.add_parser("makedata")
     m.add_argument("--threads", type=int, default=32)
     m.add_argument("--ko", action="store_true",

@@ -3,7 +3,7 @@
 One accessor per module: ``hip()`` returns ``_dghip`` (the CDNA4 kernels of the network),
 ``cpu()`` ``_dgcpu`` (Go engine, t7 codec, SGF parser, loader thread pool), ``comm()``
 ``_dgcomm`` (the RCCL communicator), and ``aug()``, ``opt()``, ``adam()``, ``lamb()``,
-``clip()``, ``ema()``, ``sched()`` the small ``_dg<name>`` modules of ``_build.SMALL``, which
+``clip()``, ``ema()``, ``sched()``, ``play()`` the small ``_dg<name>`` modules of ``_build.SMALL``, which
 only the feature that needs one imports.  On a machine with a GPU a missing or stale extension
 is a hard error: there is deliberately no silent PyTorch fallback for the GPU compute path.
 All are built by ``python -m deep_go_amd._build`` (also run by ``__graft_entry__.build()``);
@@ -87,6 +87,11 @@ def ema():
 def sched():
     """_dgsched: the learning-rate schedule's launch (csrc/kernels/sched.hip)."""
     return _load("_dgsched")
+
+
+def play():
+    """_dgplay: on-device move selection (csrc/kernels/play.hip)."""
+    return _load("_dgplay")
 
 
 def cpu():

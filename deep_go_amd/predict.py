@@ -40,6 +40,13 @@ class Prediction:
     rank: np.ndarray     # int32 [n]: rank of the label (0 = top-1; -1: no / illegal label)
 
 
+@dataclass
+class Selection:
+    move: np.ndarray     # int32 [n]: the chosen point 19*x + y (-1: no legal point / bad row)
+    p: np.ndarray        # float [n]: its tempered, renormalised probability
+    kept: np.ndarray     # int32 [n]: size of the top_p nucleus (0: no legal point, -1: bad row)
+
+
 def _gpu_usable() -> bool:
     from .ops.native import hip_available
     return torch.cuda.is_available() and hip_available()
@@ -106,6 +113,7 @@ class Predictor:
         words = m * (NUM_POINTS + 2 * K + 1)
         self._out_dev = torch.zeros(words, dtype=torch.float32, device=dev)
         self._out_host = torch.zeros(words, dtype=torch.float32).pin_memory()
+        self._sel_dev = None       # select()'s buffers, made by its first call
 
     def _out_views(self, buf: torch.Tensor):
         m, K = self.chunk, self.K
@@ -116,6 +124,8 @@ class Predictor:
 
     def _predict_gpu(self, planes, player, rank, labels, extra, mask: bool, out: Prediction,
                      lo: int):
+        # (_select_gpu repeats this upload / symmetry_planes / forward / policy_ensemble sequence
+        # with K = 1: a change here belongs there too)
         from .ops.native import stream_handle
         net, h, S = self.net, self.h, self.S
         k = len(planes)
@@ -143,6 +153,52 @@ class Predictor:
         out.topk_p[lo:lo + k] = topk_p[:k].numpy()
         out.topk[lo:lo + k] = topk[:k].numpy()
         out.rank[lo:lo + k] = rk[:k].numpy()
+
+    def _select_gpu(self, planes, player, rank, extra, game, ply, seed, temperature, top_p,
+                    out: Selection, lo: int):
+        """_predict_gpu's launches with K = 1, then policy_select on the same stream; three
+        words per position come back, the prob rows stay on the device."""
+        from .ops.native import play, stream_handle
+        net, h, S, m = self.net, self.h, self.S, self.chunk
+        if self._sel_dev is None:
+            # upload: game [m] | ply [m]; download: move [m] | p_move [m] | kept [m]
+            self._sel_host = torch.zeros(2 * m, dtype=torch.int32).pin_memory()
+            self._sel_dev = torch.zeros(2 * m, dtype=torch.int32, device=self._out_dev.device)
+            self._pick_dev = torch.zeros(3 * m, dtype=torch.int32, device=self._out_dev.device)
+            self._pick_host = torch.zeros(3 * m, dtype=torch.int32).pin_memory()
+        k = len(planes)
+        hp, hpl, hrk, hlb, hex_ = self._src_host_v
+        hp[:k] = planes.reshape(k, 9, NUM_POINTS)
+        hpl[:k], hrk[:k], hlb[:k], hex_[:k] = player, rank, -1, extra
+        hs = self._sel_host.numpy()
+        hs[:k], hs[m:m + k] = game, ply
+        self._src_dev.copy_(self._src_host, non_blocking=True)
+        self._sel_dev.copy_(self._sel_host, non_blocking=True)
+        dp, dpl, drk, dlb, dex = self._src_dev_v
+        s = stream_handle()
+        h.symmetry_planes(dp.data_ptr(), dpl.data_ptr(), drk.data_ptr(), dlb.data_ptr(), k, S,
+                          net.planes.data_ptr(), net.player.data_ptr(), net.rank.data_ptr(),
+                          net.labels.data_ptr(), net.B, s)
+        if not net._fp8_calibrated:
+            net.calibrate_fp8()
+        logp = net.predict_logp()
+        # predict()'s device output buffer, laid out for K = 1 (it holds K >= 1):
+        # prob [m, 361] | topk_p [m] | topk [m] | rank [m]
+        o1 = m * NUM_POINTS
+        prob, scratch = self._out_dev[:o1], self._out_dev[o1:o1 + 3 * m]
+        h.policy_ensemble(logp.data_ptr(), dp.data_ptr(), 9 * NUM_POINTS, dex.data_ptr(),
+                          dlb.data_ptr(), k, S, 1, 1, prob.data_ptr(),
+                          scratch[m:].data_ptr(), scratch.data_ptr(), scratch[2 * m:].data_ptr(), s)
+        pick = self._pick_dev
+        play().policy_select(prob.data_ptr(), self._sel_dev.data_ptr(),
+                             self._sel_dev[m:].data_ptr(), k, seed, temperature, top_p,
+                             pick.data_ptr(), pick[m:].data_ptr(), pick[2 * m:].data_ptr(), s)
+        self._pick_host.copy_(pick, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        got = self._pick_host.numpy()
+        out.move[lo:lo + k] = got[:k]
+        out.p[lo:lo + k] = got[m:m + k].view(np.float32)
+        out.kept[lo:lo + k] = got[2 * m:2 * m + k]
 
     # ------------------------------------------------------------------ CPU (fp32 oracle)
     def logp_cpu(self, planes: np.ndarray, player: np.ndarray, rank: np.ndarray) -> np.ndarray:
@@ -194,6 +250,44 @@ class Predictor:
         for lo in range(0, n, self.chunk):
             sl = slice(lo, min(n, lo + self.chunk))
             run(planes[sl], player[sl], rank[sl], labels[sl], extra[sl], bool(mask), out, lo)
+        return out
+
+    def select(self, planes, player, rank, extra_illegal=None, *, game, ply, seed: int = 0,
+               temperature: float = 1.0, top_p: float = 1.0) -> Selection:
+        """One move per position, drawn from predict()'s masked distribution (mask=True) with a
+        temperature and a nucleus cut: play/select.py is the definition.  game [n] and ply [n]
+        (int32) key the draw together with seed, so a position's move does not depend on the
+        chunk or slot that carries it.  On the GPU the selection runs on the device
+        (csrc/kernels/play.hip) and three words per position are downloaded."""
+        planes = np.ascontiguousarray(np.asarray(planes, np.uint8)).reshape(-1, 9, 19, 19)
+        n = len(planes)
+        player = np.asarray(player, np.uint8).reshape(n)
+        rank = np.asarray(rank, np.uint8).reshape(n)
+        game = np.asarray(game, np.int32).reshape(n)
+        ply = np.asarray(ply, np.int32).reshape(n)
+        extra = (np.zeros((n, NUM_POINTS), np.uint8) if extra_illegal is None
+                 else (np.asarray(extra_illegal).reshape(n, NUM_POINTS) != 0).astype(np.uint8))
+        seed, T, top_p = int(seed) & (2 ** 64 - 1), float(temperature), float(top_p)
+        if not (np.isfinite(T) and T >= 0):
+            raise ValueError(f"temperature = {temperature}: expected a finite value >= 0")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"top_p = {top_p}: expected a value in (0, 1]")
+        gpu = self.device == "gpu"
+        out = Selection(np.full(n, -1, np.int32), np.zeros(n, np.float32 if gpu else np.float64),
+                        np.zeros(n, np.int32))
+        for lo in range(0, n, self.chunk):
+            sl = slice(lo, min(n, lo + self.chunk))
+            if gpu:
+                self._select_gpu(planes[sl], player[sl], rank[sl], extra[sl], game[sl], ply[sl],
+                                 seed, T, top_p, out, lo)
+            else:
+                from .play.select import select_moves
+                k = sl.stop - sl.start
+                logp = self.logp_cpu(planes[sl], player[sl], rank[sl])
+                legal = (planes[sl, 0].reshape(k, NUM_POINTS) == 0) & (extra[sl] == 0)
+                prob = ensemble_policy(logp, legal, 1)[0]
+                out.move[sl], out.p[sl], out.kept[sl] = select_moves(prob, game[sl], ply[sl],
+                                                                     seed, T, top_p)
         return out
 
 

@@ -13,3 +13,10 @@ for SAN in thread address,undefined; do
   TSAN_OPTIONS="halt_on_error=1" ASAN_OPTIONS="detect_leaks=1:halt_on_error=1" \
     UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1" timeout 600 $OUT
 done
+# the live game (dg::Game): random legal games with undo, masks and scoring
+OUT=$OUTDIR/game_address_undefined
+g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined \
+  csrc/engine/tests/game_main.cpp csrc/engine/go_engine.cpp -o $OUT
+echo "== game, -fsanitize=address,undefined"
+ASAN_OPTIONS="detect_leaks=1:halt_on_error=1" UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1" \
+  timeout 600 $OUT
